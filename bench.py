@@ -29,6 +29,17 @@ same launch shape (per packet, scaled), when one exists.  `cpu_baseline` = the o
 ACL) timed on this host's cores as pinned run-to-completion pthreads (rank 0, N = 1).
 
 `--dry-run`: the rank plumbing only (gloo, no GPU): spawn, rendezvous, MAX reduction, one JSON line.
+
+A plain run (`--gpus 1 --steps K --warmup W`) does only what `value` needs: it builds the resident batches, warms up,
+times the K steps and prints the line (`value`, `ms_per_step`, the roofline of the timed launch itself).  `--full`
+adds everything else described above and nests it in the same line: the dispatch-timestamp launch and the same-run
+memory ceilings, the parity samples against the oracle, the CPU baselines, the host-inclusive rate, the rule-commit
+and lookup latencies, the verdict gather (N > 1), C0, C2 - C4 and the stateful configs F1 / D1.
+
+`--dump-outputs DIR`: after the timed steps, what the last timed step computed is written as DIR/<name>.npy (rank
+0; float32 / float64, at most 64 MB in all): verdict, flow_hash, acl_hit and part8 (the compact partition list) of
+its batch for the stateless configs and F1; status, dgram_of, n_dgram, dgram_len and the first datagrams' bytes for
+D1.  The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -78,6 +89,29 @@ def free_port() -> int:
         return s.getsockname()[1]
 
 
+DUMP_BUDGET = 64 << 20  # --dump-outputs: bytes written in all
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: `arrays` (name -> integer array, first axis = packet / fragment / datagram) as path/<name>.npy.
+    Words of up to 16 bits go out as float32, wider ones as float64 (both exact).  If the files would exceed
+    DUMP_BUDGET together, every array is cut to the same fraction of its rows, a sorted sample drawn with the fixed
+    seed synth.SEED (arrays of one length keep the same rows), so two builds dump the same rows."""
+    path = Path(path)
+    path.mkdir(parents=True, exist_ok=True)
+    conv = {}
+    for k, a in arrays.items():
+        a = np.atleast_1d(np.asarray(a))
+        conv[k] = a.astype(np.float32 if a.dtype.itemsize <= 2 else np.float64)
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_BUDGET:
+        for k, a in conv.items():
+            rows = max(1, int(len(a) * (DUMP_BUDGET - 4096 * len(conv)) / total))
+            conv[k] = a[np.sort(np.random.default_rng(synth.SEED).choice(len(a), rows, replace=False))]
+    for k, a in conv.items():
+        np.save(path / f"{k}.npy", a)
+
+
 def spawn(args_list: list[str], n: int) -> int:
     """Run this script under torch.distributed.run with n ranks (a child process: this one never touched the GPU)."""
     # torch.distributed.run's own parser would take `--n` as an ambiguous abbreviation of its options
@@ -120,6 +154,14 @@ def parse(argv=None):
                     help="CPU baseline sample length of each nested stateless config (all cores)")
     ap.add_argument("--no-c0", action="store_true", help="skip the C0 plumbing config (10k x 64 B, 16 rules)")
     ap.add_argument("--dry-run", action="store_true", help="rank plumbing only (gloo, no GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure as well: the dispatch-timestamp launch and same-run "
+                         "memory ceilings of the roofline, parity samples against the oracle, CPU baselines, the "
+                         "host-inclusive rate, rule-commit and lookup latencies, the verdict gather (N > 1), C0 and "
+                         "the nested configs (--configs, --stateful)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the arrays its caller "
+                         "receives) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     ap.add_argument("--shared-gpu", action="store_true",
                     help="rehearsal of the N > 1 path on a one-GPU box: every rank on cuda:0, collectives over gloo "
                          "(the rates are not a scaling result; stateless configs only)")
@@ -196,13 +238,16 @@ class Resident:
                                                 kind=cfgd["kind"], stride=stride))
         self.bufs = []
         reps = (n + gen_n - 1) // gen_n
+        # (each generated batch crosses to the device once; every buffer is then a device-side copy of its own)
+        src = [(torch.from_numpy(pk["hdr"]).to(dev), torch.from_numpy(pk["len"].view(np.int32)).to(dev))
+               for pk in self.host]
         for b in range(nbufs):
-            pk = self.host[b % 2]
-            hdr = torch.from_numpy(pk["hdr"]).to(dev)
-            lens = torch.from_numpy(pk["len"].view(np.int32)).to(dev)
+            hdr, lens = src[b % 2]
             if reps > 1:
                 hdr = hdr.repeat(reps, 1)[:n].contiguous()
                 lens = lens.repeat(reps)[:n].contiguous()
+            else:
+                hdr, lens = hdr.clone(), lens.clone()
             if layout == "packed":  # one 8-B word per packet: include/ppe_hip.h PPE_PACKED_*
                 out = {"packed": torch.empty(n, dtype=torch.int64, device=dev)}
             else:
@@ -215,6 +260,7 @@ class Resident:
             rr = abi.Result(ptr("verdict"), ptr("flow_hash"), ptr("acl_hit"), None, None, None, None,
                             out["part8"].data_ptr(), ptr("packed"))
             self.bufs.append((hdr, lens, out, bb, rr))
+        del src
         lens0 = self.host[0]["len"].astype(np.int64)
         self.read_bytes_per_pkt = float(np.minimum(lens0 & 0xFFFF, 64).mean() + 4.0) if stride == 64 else None
         # algorithmic result bytes (the verdict, flow hash and ACL hit: 12 B as three words, 8 B
@@ -660,7 +706,9 @@ def measure_config(name, args, dev, world, rank, dist, primary):
     per_buf = n * (stride + 4 + 16)
     # distinct resident batches: more than twice the 256 MiB Infinity Cache, and at least as many as one launch takes
     # (a launch's batch groups run concurrently, so a buffer repeated inside one launch would be re-read from cache)
-    nbufs = args.nbufs or max(8, int(np.ceil(600e6 / per_buf)), args.steps, max(args.warmup, 1))
+    # (up to 64 of them by default: a run of thousands of steps rotates over 64 buffers, gigabytes between two uses
+    # of one buffer, instead of holding one resident batch per step)
+    nbufs = args.nbufs or max(8, int(np.ceil(600e6 / per_buf)), min(64, max(args.steps, args.warmup, 1)))
     eng = Engine(dev.index)
     eng.tuning(batches_per_launch=args.batches_per_launch)
     acl = eng.commit(rules, default_action=1)
@@ -702,14 +750,21 @@ def measure_config(name, args, dev, world, rank, dist, primary):
     bpl = args.batches_per_launch or args.steps
     launches = -(-args.steps // bpl)
     kern_ms = my_ms
-    # the kernel alone: the same call again with the dispatch's own start / end timestamps (hipExtLaunchKernelGGL)
-    eng.timing(True)
-    eng.timing_read(reset=True)
-    barrier()
-    run(timed)
-    barrier()
-    disp_ms, disp_launches = eng.timing_read(reset=True)
-    eng.timing(False)
+    if primary and rank == 0 and args.dump_outputs:
+        # the last timed step's batch, as its caller receives it (copied out before anything else touches the buffers)
+        last = (args.steps - 1) % nbufs
+        dump_outputs(args.dump_outputs, {**res.results(last), "part8": res.bufs[last][2]["part8"].cpu().numpy()})
+    # --full: the kernel alone, the same call again with the dispatch's own start / end timestamps
+    # (hipExtLaunchKernelGGL)
+    disp_ms, disp_launches = 0.0, 0
+    if args.full:
+        eng.timing(True)
+        eng.timing_read(reset=True)
+        barrier()
+        run(timed)
+        barrier()
+        disp_ms, disp_launches = eng.timing_read(reset=True)
+        eng.timing(False)
     if dist is not None:
         t = torch.tensor([my_ms, kern_ms, disp_ms], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -726,7 +781,7 @@ def measure_config(name, args, dev, world, rank, dist, primary):
     disp_avg_ms = disp_ms / max(disp_launches, 1)
     achieved = alg * pk_launch / (kern_avg_ms / 1e3) / 1e9
     tpp = traffic_per_packet(name)
-    parity, psample = parity_sample(eng, res, rules, name) if rank == 0 else (None, 0)
+    parity, psample = parity_sample(eng, res, rules, name) if rank == 0 and args.full else (None, 0)
     out = {
         "value": round(mpps, 2), "unit": "Mpps", "ms_per_step": round(my_ms / args.steps, 5),
         "workload": f"{name}: {n} x {'64B IPv4/UDP' if cfgd['kind'] == 'udp64' else 'IMIX 64/570/1500B Eth+VLAN TCP/UDP'}"
@@ -742,23 +797,25 @@ def measure_config(name, args, dev, world, rank, dist, primary):
                      "bytes_per_pkt": round(alg, 3), "read_bytes_per_pkt": round(rd, 3),
                      "written_bytes_per_pkt": res.written_bytes, "result_layout": args.layout,
                      "read_frac": round(rd * pk_launch / (kern_avg_ms / 1e3) / 1e9 / HBM_PEAK_GBPS, 4),
-                     "us_per_1M_packets": round(kern_avg_ms * 1e3 / (pk_launch / (1 << 20)), 3),
-                     "dispatch": {"kernel_avg_us": round(disp_avg_ms * 1e3, 3), "launches": disp_launches,
-                                  "us_per_1M_packets": round(disp_avg_ms * 1e3 / (pk_launch / (1 << 20)), 3),
-                                  "frac": round(alg * pk_launch / (disp_avg_ms / 1e3) / 1e9 / HBM_PEAK_GBPS, 4),
-                                  "timing": "the same call again with the dispatch packet's start / end timestamps "
-                                            "(hipExtLaunchKernelGGL events: what rocprofv3 reports): the kernel alone"}},
-        "parity_sample_ok": parity, "parity_sample_packets": psample,
+                     "us_per_1M_packets": round(kern_avg_ms * 1e3 / (pk_launch / (1 << 20)), 3)},
         "acl": {**{k: acl[k] for k in ("n_rules", "n_nodes", "max_depth", "blob_bytes", "lds_resident")},
                 "build_ms": round(acl["build_ms"], 3)},
         "launch": eng.launch_info(),
     }
-    if primary and rank == 0:
+    if args.full:
+        out["roofline"]["dispatch"] = {
+            "kernel_avg_us": round(disp_avg_ms * 1e3, 3), "launches": disp_launches,
+            "us_per_1M_packets": round(disp_avg_ms * 1e3 / (pk_launch / (1 << 20)), 3),
+            "frac": round(alg * pk_launch / (disp_avg_ms / 1e3) / 1e9 / HBM_PEAK_GBPS, 4),
+            "timing": "the same call again with the dispatch packet's start / end timestamps "
+                      "(hipExtLaunchKernelGGL events: what rocprofv3 reports): the kernel alone"}
+        out["parity_sample_ok"], out["parity_sample_packets"] = parity, psample
+    if args.full and primary and rank == 0:
         try:
             out["roofline"]["ceiling"] = ceiling(res, args, dev, disp_avg_ms, pk_launch, alg)
         except Exception as e:  # the ceiling is context, never worth losing the line over
             out["roofline"]["ceiling"] = {"error": str(e)[:200]}
-    if not primary and rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and not primary and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(res.host[0], rules, eng.image(), args.nested_cpu_seconds, name)
     ctx = dict(eng=eng, res=res, rules=rules, cfg=cfg, n=n, my_ms=my_ms)
     if not primary:
@@ -777,7 +834,7 @@ def run_stateless(args, dev, world, rank, dist):
     # exchanges nothing): all_gather over RCCL of one batch's verdict + flow hash + ACL hit (8 B per packet packed,
     # 12 B as three words)
     gather = None
-    if dist is not None:
+    if dist is not None and args.full:
         try:
             out0 = res.bufs[0][2]
             src = (out0["packed"].view(1, -1) if res.layout == "packed"
@@ -823,13 +880,13 @@ def run_stateless(args, dev, world, rank, dist):
 
     # live rule commit: host build + upload + publish of the same rule set between batches
     commit_ms = []
-    for _ in range(3):
+    for _ in range(3 if args.full else 0):
         tc0 = time.perf_counter()
         eng.commit(rules, default_action=1)
         commit_ms.append((time.perf_counter() - tc0) * 1e3)
 
     lookup = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             lookup = acl_lookup_latency(eng, res.host[0], rules)
         except Exception as e:
@@ -837,7 +894,7 @@ def run_stateless(args, dev, world, rank, dist):
 
     # host-inclusive rate (pinned host buffers: the kernel reads / writes them across PCIe), rank 0 at N = 1
     host_mpps = None
-    if rank == 0 and world == 1 and not args.no_host_inclusive:
+    if rank == 0 and world == 1 and args.full and not args.no_host_inclusive:
         import ctypes as C
         from ppe import abi
         pk = res.host[0]
@@ -863,19 +920,19 @@ def run_stateless(args, dev, world, rank, dist):
     # CPU baseline: the oracle's C restatement (tree-walk ACL over the same classifier image), rank 0, N = 1: all of
     # this host's cores (nproc) as pinned run-to-completion shards, then one pinned thread
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(res.host[0], rules, eng.image(), args.cpu_seconds, args.config)
 
     eng.close()
     del res
     torch.cuda.empty_cache()
     extra = {}
-    if rank == 0 and world == 1 and args.n == 0 and not args.no_c0:
+    if rank == 0 and world == 1 and args.n == 0 and args.full and not args.no_c0:
         try:
             extra["C0"] = measure_c0(args, dev)
         except Exception as e:
             extra["C0"] = {"error": str(e)[:300]}
-    names = [c for c in args.configs.split(",") if c and c != args.config] if args.n == 0 else []
+    names = [c for c in args.configs.split(",") if c and c != args.config] if args.n == 0 and args.full else []
     for name in names:
         try:
             extra[name], _ = measure_config(name, args, dev, world, rank, dist, primary=False)
@@ -885,7 +942,7 @@ def run_stateless(args, dev, world, rank, dist):
             extra[name] = {"error": str(e)[:300]}
     # the stateful paths: the flow table (FlowHandlePacket) and IPv4 reassembly
     # (Defrag), each with its own roofline and parity sample
-    for name in [c for c in args.stateful.split(",") if c] if args.n == 0 else []:
+    for name in [c for c in args.stateful.split(",") if c] if args.n == 0 and args.full else []:
         fn = run_flow if "flows" in synth.CONFIGS[name] else run_defrag
         try:
             extra[name] = fn(args, synth.CONFIGS[name], dev, world, rank, dist, name=name, nested=True)
@@ -910,14 +967,18 @@ def run_stateless(args, dev, world, rank, dist):
                                          "soa: 4-B verdict, flow hash, ACL hit + 1-B compact partition list"),
                        "parallelism": f"batch-sharded x{world}"},
             "roofline": rf,
-            "cpu_baseline": cpu,
-            "host_inclusive_mpps": round(host_mpps, 2) if host_mpps else None,
-            "parity_sample_ok": line_cfg["parity_sample_ok"],
             "ranks_reported": dist.get_world_size() if dist is not None else 1,
-            "acl": {**line_cfg["acl"], "commit_ms": round(float(np.median(commit_ms)), 3), **(lookup or {})},
+            "acl": line_cfg["acl"],
             "launch": line_cfg["launch"],
-            "configs": extra,
         }
+        if args.full:
+            line.update({
+                "cpu_baseline": cpu,
+                "host_inclusive_mpps": round(host_mpps, 2) if host_mpps else None,
+                "parity_sample_ok": line_cfg["parity_sample_ok"],
+                "acl": {**line_cfg["acl"], "commit_ms": round(float(np.median(commit_ms)), 3), **(lookup or {})},
+                "configs": extra,
+            })
         if gather is not None:
             line["gather"] = gather
         if args.shared_gpu:
@@ -970,7 +1031,7 @@ def run_flow(args, cfgd, dev, world, rank, dist, name=None, nested=False):
 
     # parity sample first: a fresh table, four 64k batches, against the oracle's sequential flow table
     parity = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:  # (rank 0 only, no collectives: an error here must not leave the other ranks in a barrier)
             import pyoracle
             m = 1 << 16
@@ -1074,31 +1135,39 @@ def run_flow(args, cfgd, dev, world, rank, dist, name=None, nested=False):
     cnt = eng.counters()
     new_timed = eng.flow_info()["new_flow"] - new0
     info = eng.flow_info()
-    # the classify (FlowFind) kernel alone: the dispatch timestamps (hipExtLaunchKernelGGL events) of K more batches
-    # over the same flows (their packet times follow the timed ones'); a steered rank's launches are its own share of
-    # every batch
-    eng.timing(True)
-    eng.timing_read(reset=True)
-    barrier()
-    for i in range(args.steps):
-        step(args.warmup + args.steps + i)
-    barrier()
-    kern_ms, launches = eng.timing_read(reset=True)
-    eng.timing(False)
+    if rank == 0 and not nested and not steer and args.dump_outputs:
+        # the last timed batch's results and compact partition list
+        _, _, lo, lp, _ = bufs[(args.warmup + args.steps - 1) % nbufs]
+        lo = lo.cpu().numpy()
+        dump_outputs(args.dump_outputs, {"verdict": lo[0].view(np.uint32), "flow_hash": lo[1].view(np.uint32),
+                                         "acl_hit": lo[2], "part8": lp.cpu().numpy()})
+    # --full: the classify (FlowFind) kernel alone: the dispatch timestamps (hipExtLaunchKernelGGL events) of K more
+    # batches over the same flows (their packet times follow the timed ones'); a steered rank's launches are its own
+    # share of every batch
+    kern_ms, launches = 0.0, 0
+    if args.full:
+        eng.timing(True)
+        eng.timing_read(reset=True)
+        barrier()
+        for i in range(args.steps):
+            step(args.warmup + args.steps + i)
+        barrier()
+        kern_ms, launches = eng.timing_read(reset=True)
+        eng.timing(False)
     if dist is not None:
         t = torch.tensor([my_ms], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         my_ms = float(t.item())
     mpps = n * args.steps * world / (my_ms / 1e3) / 1e6
-    kern_avg_ms = kern_ms / max(launches, 1)
+    kern_avg_ms = kern_ms / launches if launches else None  # (None without --full: no dispatch timestamps taken)
     owner = flow_owner_update()
     bpp = flow_bytes(stride, owner)
-    achieved = bpp * n / (kern_avg_ms / 1e3) / 1e9
+    achieved = bpp * n / (kern_avg_ms / 1e3) / 1e9 if kern_avg_ms else None
     # the whole batch (classify, flow kernels, update) against the in-kernel definition's bytes: the batch roofline
     batch_achieved = flow_bytes(stride) * n / (my_ms / args.steps / 1e3) / 1e9
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = flow_cpu_baseline(bufs[0][4], rules, eng.image(), flows,
                                 args.nested_cpu_seconds if nested else args.cpu_seconds)
 
@@ -1113,16 +1182,17 @@ def run_flow(args, cfgd, dev, world, rank, dist, name=None, nested=False):
                                    f"bidirectional flows, {cfgd['rules']} five-tuple ACL rules, default FW",
                        "packets_per_gpu": n, "flows": flows, "rules": cfgd["rules"], "resident_batches": nbufs,
                        "parallelism": f"flow-sharded x{world}" + (" (all-to-all steering by flow hash)" if steer else "")},
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBPS, 4),
+            "roofline": {"bound": "hbm", "achieved": round(achieved, 1) if achieved else None,
+                         "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                         "frac": round(achieved / HBM_PEAK_GBPS, 4) if achieved else None,
                          "traffic": round(tpp * n) if tpp else None,
                          "kernel": "ppe_classify_kernel<FLOW> (FlowFind; found flows' updates "
                                    + ("to the owners' buckets, applied beside finalize by ppe_flow_post_kernel" if owner else
                                       "by one atomic per packet") + "; misses resolved by the flow kernels)",
-                         "kernel_avg_us": round(kern_avg_ms * 1e3, 3), "bytes_per_pkt": bpp,
+                         "kernel_avg_us": round(kern_avg_ms * 1e3, 3) if kern_avg_ms else None, "bytes_per_pkt": bpp,
                          "timing": "batch_avg_us and value: the timed region's HIP events around its K batches (no "
                                    "dispatch events inside); kernel_avg_us: the dispatch timestamps of the classify "
-                                   "launches of K more batches over the same flows, run right after it",
+                                   "launches of K more batches over the same flows, run right after it (--full)",
                          "batch_avg_us": round(my_ms / args.steps * 1e3, 3),
                          "batch_bytes_per_pkt": flow_bytes(stride),
                          "batch_frac": round(batch_achieved / HBM_PEAK_GBPS, 4),
@@ -1207,7 +1277,7 @@ def run_defrag(args, cfgd, dev, world, rank, dist, name=None, nested=False):
 
     # parity sample: batch variant 1 through a fresh table and the oracle's sequential Defrag
     parity, stats = None, None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:  # (rank 0 only, no collectives: an error here must not leave the other ranks in a barrier)
             import pyoracle
             g = Defrag(eng, fcb_max=1 << 16)
@@ -1275,6 +1345,16 @@ def run_defrag(args, cfgd, dev, world, rank, dist, name=None, nested=False):
     dlen = out["dgram_len"][:n_dgram].to(torch.int64).sum().item()
     st = out["status"].cpu().numpy().view(np.uint32) & 0xff
     held = int(np.isin(st, (0, 1, 2)).sum())
+    if rank == 0 and not nested and args.dump_outputs:
+        # the last timed call's outputs: every fragment's status and datagram index, the datagrams' lengths, and the
+        # first 512 reassembled datagrams' bytes (zero past each one's length: the rest of a row is not output)
+        nd = min(n_dgram, 512)
+        dl = out["dgram_len"][:n_dgram].cpu().numpy().view(np.uint32)
+        dp = out["dgram_pkt"][:nd].cpu().numpy()
+        dp = np.where(np.arange(dp.shape[1])[None, :] < dl[:nd, None], dp, 0).astype(np.uint8)
+        dump_outputs(args.dump_outputs, {"status": out["status"].cpu().numpy().view(np.uint32),
+                                         "dgram_of": out["dgram_of"].cpu().numpy().view(np.uint32),
+                                         "n_dgram": np.array([n_dgram], np.uint32), "dgram_len": dl, "dgram_pkt": dp})
     if dist is not None:
         t = torch.tensor([my_ms], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -1299,7 +1379,7 @@ def run_defrag(args, cfgd, dev, world, rank, dist, name=None, nested=False):
     achieved = bytes_call / (call_ms / 1e3) / 1e9
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = defrag_cpu_baseline(variant, off, lens, cfgd["fcb_max"],
                                   args.nested_cpu_seconds if nested else args.cpu_seconds)
 

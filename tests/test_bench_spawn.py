@@ -51,8 +51,8 @@ def test_two_ranks_on_one_gpu():
     """The N > 1 path end to end on real kernels (a one-GPU box: both ranks on cuda:0, gloo collectives): each rank
     classifies its own resident batches, its parity sample is green, the MAX-over-ranks line counts both ranks'
     packets, and the verdict gather runs.  RCCL itself is the driver's multi-GPU run."""
-    r = run(["--gpus", "2", "--shared-gpu", "--n", "262144", "--steps", "8", "--warmup", "2", "--configs", "",
-             "--no-cpu-baseline", "--no-host-inclusive"], timeout=110)
+    r = run(["--gpus", "2", "--shared-gpu", "--full", "--n", "262144", "--steps", "8", "--warmup", "2",
+             "--configs", "", "--no-cpu-baseline", "--no-host-inclusive"], timeout=110)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = json_lines(r.stdout)
     assert len(lines) == 1, r.stdout

@@ -13,6 +13,6 @@ if [ -n "$TF" ]; then
   timeout -k 10 600 python -u -m pytest -x -v --timeout 120 --timeout-method thread $TF > $O/pytest.txt 2>&1 || exit 1
 fi
 for i in 1 2; do
-  PPE_LIB=$OLD timeout -k 10 300 python bench.py --config $C --no-cpu-baseline "$@" > $O/old_$i.json 2> $O/old_$i.err || exit 1
-  timeout -k 10 300 python bench.py --config $C --no-cpu-baseline "$@" > $O/new_$i.json 2> $O/new_$i.err || exit 1
+  PPE_LIB=$OLD timeout -k 10 300 python bench.py --full --config $C --no-cpu-baseline "$@" > $O/old_$i.json 2> $O/old_$i.err || exit 1
+  timeout -k 10 300 python bench.py --full --config $C --no-cpu-baseline "$@" > $O/new_$i.json 2> $O/new_$i.err || exit 1
 done

@@ -6,7 +6,7 @@ T=${1:-x}
 O=gpurun_out/pmc_$T
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-P="bench.py --steps 20 --warmup 2 --no-cpu-baseline --no-host-inclusive"
+P="bench.py --full --steps 20 --warmup 2 --no-cpu-baseline --no-host-inclusive"
 rocprofv3 -L > $O/counters_list.txt 2>&1 || true
 i=0
 for G in "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_MISC SQ_INST_CYCLES_SALU SQ_BUSY_CYCLES SQ_WAVES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE GRBM_COUNT" \

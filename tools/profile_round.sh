@@ -17,7 +17,7 @@ if [ ! -f $O/cal_fetch/cal_counter_collection.csv ]; then
   timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/cal_write -o cal -- tools/calib/stream_calib 1048576 4 > $O/cal_write.log 2>&1 || exit 1
 fi
 for C in $CONFIGS; do
-  B="bench.py --config $C --configs= --stateful= --warmup $K --steps $K --no-cpu-baseline --no-host-inclusive"
+  B="bench.py --full --config $C --configs= --stateful= --warmup $K --steps $K --no-cpu-baseline --no-host-inclusive"
   R="tools/ring_run.py --config $C --batches $K --launches 3"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$C -o k -- python3 $B > $O/kt_$C.log 2>&1 || exit 1
   timeout -s KILL 150 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/fetch_$C -o k -- python3 $R > $O/fetch_$C.log 2>&1 || exit 1
