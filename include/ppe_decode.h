@@ -136,6 +136,11 @@ void ppe_set_output_hooks(ppe_output_fn fw, ppe_output_fn drop, ppe_output_fn pu
 /* config knobs pushed by the manager in the reference (dp_cmd.c:37 unsupport_proto_action, flow.c:26 syn_check) */
 extern uint32_t unsupport_proto_action;
 extern uint32_t syn_check;
+/* StreamTcp's settings (stream-tcp.c:16,20-21), read per classify call like syn_check.  All start at 0 here (tracking
+ * OFF; the reference starts with stream_tcp_track_enable = 1): see ppe_stream_tcp_set in ppe_hip.h */
+extern uint32_t stream_tcp_track_enable;
+extern uint32_t stream_tcp_midstream;
+extern uint32_t stream_tcp_async_oneside;
 
 void Decode(mbuf_t *m);
 /* Classify every mbuf the calling thread has queued; returns the number delivered through the output hooks, or a

@@ -38,7 +38,8 @@ extern "C" {
  * 3: ppe_tuple's word 3 carries the TCP window-scale option offset (bits 9-15); 4: ppe_result_t.part8;
  * 5: the tuple carries a fragment's Defrag fields and the option-past-the-window bit; strides 64..256;
  * 6: ppe_acl_stats_t cut fields; 7: ppe_rules_stage / _publish; 8: ppe_result_t.packed (8-B verdict + flow hash +
- * ACL hit) */
+ * ACL hit); additive within 8 (no existing struct or value changes): the StreamTcp first-packet verdict
+ * (ppe_stream_tcp_*, statuses 20-23, ppe_stream_counters_*, ppe_format_tcpstream_stat), off until set */
 #define PPE_ABI_VERSION 8
 
 /* error codes (negative return values) */
@@ -72,7 +73,14 @@ enum ppe_status {
     PPE_ST_FLOW_TCP_NO_SYN_FIRST = 17, /* flow miss, TCP without SYN, syn_check on        flow.c:204-214               */
     PPE_ST_WINDOW_PUNT = 18,      /* needed header bytes lie beyond the header window (engine-specific PUNT)          */
     PPE_ST_FLOW_NOMEM = 19,       /* flow table: ACL passed but the flow pool is exhausted  STAT_FLOW_NODE_NOMEM flow.c:127 */
-    PPE_ST__COUNT = 20
+    /* StreamTcp's verdict for a packet without a session (StreamTcpPacketStateNone, dataplane/src/plugin/stream-tcp/
+     * stream-tcp.c:237-441), only with ppe_stream_tcp_set tracking on: the ACL forwarded the packet, then
+     * STREAMTCP_ERR → output_drop_proc (flow.c:311-320).  acl_hit, PPE_F_ACL and the tuple keep the ACL's results. */
+    PPE_ST_STREAM_RST_NO_SESSION = 20,        /* RST                        STREAM_RST_BUT_NO_SESSION  stream-tcp.c:243-248 */
+    PPE_ST_STREAM_FIN_NO_SESSION = 21,        /* FIN                        STREAM_FIN_BUT_NO_SESSION  stream-tcp.c:249-254 */
+    PPE_ST_STREAM_MIDSTREAM_ONESIDE_OFF = 22, /* SYN|ACK, midstream and async_oneside both 0           stream-tcp.c:255-261 */
+    PPE_ST_STREAM_MIDSTREAM_OFF = 23,         /* ACK without SYN, midstream 0                           stream-tcp.c:364-370 */
+    PPE_ST__COUNT = 24
 };
 
 enum ppe_action { PPE_ACT_FW = 0, PPE_ACT_DROP = 1, PPE_ACT_PUNT = 2 };
@@ -264,6 +272,40 @@ int   ppe_sync(ppe_ctx_t *ctx);
 /* Counters: per-workgroup slots in device memory, reduced on read.  Synchronises the device. */
 int  ppe_counters_read(ppe_ctx_t *ctx, ppe_counters_t *out);
 int  ppe_counters_clear(ppe_ctx_t *ctx);
+
+/* ---- StreamTcp's first-packet verdict on the stateless classify path (dataplane/src/plugin/stream-tcp/stream-tcp.c) ----
+ * The reference runs every TCP packet the ACL forwarded through StreamTcp (flow.c:311-320); for a packet without a
+ * session the decision is StreamTcpPacketStateNone (stream-tcp.c:237-441), a function of th_flags and these words.
+ * The stateless path treats every packet as the first of its flow, so with track = 1 ppe_classify,
+ * ppe_classify_batches and ppe_classify_host apply that decision to every TCP packet with status PPE_ST_ACL_FW:
+ *   RST → PPE_ST_STREAM_RST_NO_SESSION; else FIN → PPE_ST_STREAM_FIN_NO_SESSION; else SYN|ACK →
+ *   PPE_ST_STREAM_MIDSTREAM_ONESIDE_OFF unless midstream or async_oneside; else SYN → forward; else ACK →
+ *   PPE_ST_STREAM_MIDSTREAM_OFF (midstream 0); anything else forwards (stream-tcp.c:434-437).
+ * A stream drop keeps acl_hit, PPE_F_ACL, the flow hash, the tuple and every flag, and counts in ppe_counters_t what
+ * the reference has counted by then: ACL_FW (flow.c:240), FLOW_PROC_OK (flow.c:309), OUT_DROP; not FLOW_PROC_FAIL.
+ * A new context starts at {0,0,0,0} (tracking off: results and counters exactly as without this interface; the
+ * reference itself starts with tracking on, stream-tcp.c:16,20-21).  ppe_stream_tcp_set(ctx, NULL) selects the
+ * reference's defaults {1,0,0,1}; a word above 1 is PPE_EINVAL.  reasm only feeds ppe_format_tcpstream_stat.  The
+ * setting travels by value with each launch: it applies to launches enqueued after the call, no synchronisation.
+ * Not supported (PPE_ENOTSUP): track && midstream && !syn_check on the stateless calls (an ACK-only packet would
+ * enter segment reassembly, stream-tcp.c:371-432), and ppe_classify_flow with track (later packets of a flow need the
+ * session state machine, stream-tcp.c:3005-3140); the flow table stays usable. */
+typedef struct { uint32_t track, midstream, async_oneside, reasm; } ppe_stream_tcp_cfg_t;
+int  ppe_stream_tcp_set(ppe_ctx_t *ctx, const ppe_stream_tcp_cfg_t *cfg);
+int  ppe_stream_tcp_get(ppe_ctx_t *ctx, ppe_stream_tcp_cfg_t *cfg);
+
+/* tcpstreamtrackstat counters this path produces (STREAM_* macros, stream-tcp.c:2989-3003 counted for every tracked
+ * packet before the decision, then one per drop reason); SESSION_NO_MEM has no stateless meaning and stays 0 */
+enum ppe_stream_counter { PPE_SC_SYN_ACK_COUNT, PPE_SC_SYN_COUNT, PPE_SC_RST_COUNT, PPE_SC_RST_BUT_NO_SESSION,
+  PPE_SC_FIN_BUT_NO_SESSION, PPE_SC_MIDSTREAM_OR_ONESIDE_DISABLE, PPE_SC_MIDSTREAM_DISABLE, PPE_SC_PKT_BROKEN_ACK,
+  PPE_SC__COUNT };
+typedef struct { uint64_t c[16]; } ppe_stream_counters_t;   /* indexed by enum ppe_stream_counter; the rest 0 */
+int  ppe_stream_counters_read(ppe_ctx_t *ctx, ppe_stream_counters_t *out);   /* synchronises, like ppe_counters_read */
+int  ppe_stream_counters_clear(ppe_ctx_t *ctx);                              /* dp_clear_tcpstream_stat, dp_cmd.c:156 */
+/* `show tcpstream statistic` text (dp_show_tcpstream_stat, dp_cmd.c:174-842: same lines, order and labels; the
+ * enable / disable lines from cfg->track and cfg->reasm, NULL cfg = both disabled; counters this engine does not
+ * produce print 0).  snprintf semantics, like ppe_format_pkt_stat. */
+int  ppe_format_tcpstream_stat(const ppe_stream_counters_t *c, const ppe_stream_tcp_cfg_t *cfg, char *buf, size_t cap);
 
 /* Kernel timing with HIP events recorded around each ppe_classify launch on its stream. */
 int  ppe_timing_enable(ppe_ctx_t *ctx, int on);

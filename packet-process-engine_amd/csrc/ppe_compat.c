@@ -25,6 +25,12 @@ uint32_t dp_acl_action_default = ACL_RULE_ACTION_DROP;
 int gWstDepth = 0, gAvgDepth = 0, gChildCount = 0, gNumTreeNode = 0, gNumLeafNode = 0;
 uint32_t unsupport_proto_action = 0; /* dataplane/src/common/dp_cmd.c:37 */
 uint32_t syn_check = 1;              /* dataplane/src/flow/flow.c:26 */
+/* StreamTcp's settings (dataplane/src/plugin/stream-tcp/stream-tcp.c:16,20-21), read per classify call.  The reference
+ * starts with tracking on; this library starts with it OFF, so that a dataplane linked against it keeps the verdicts
+ * it had: set stream_tcp_track_enable = 1 for the reference's default behaviour. */
+uint32_t stream_tcp_track_enable = 0;
+uint32_t stream_tcp_midstream = 0;
+uint32_t stream_tcp_async_oneside = 0;
 PluginModule plugin_modules[PLUGIN_SIZE];
 
 struct ppe_tree_set {
@@ -314,7 +320,8 @@ void Decode_Set_Burst(uint32_t n) {
     if (n) __atomic_store_n(&g_burst_cap, n, __ATOMIC_RELAXED);
 }
 
-/* statuses on which the reference calls DP_Log_Func before dropping */
+/* statuses on which the reference calls DP_Log_Func before dropping (not StreamTcp's drops, PPE_ST_STREAM_*:
+ * flow.c:316-319 goes to output_drop_proc without it) */
 static int logged_drop(uint32_t st) {
     switch (st) {
         case PPE_ST_L2_HEADER_ERR: case PPE_ST_VLAN_HEADER_ERR: case PPE_ST_IPV4_HEADER_ERR:
@@ -390,8 +397,9 @@ static void fill_mbuf(mbuf_t *m, uint32_t v, uint32_t fhash, int32_t hit, const 
         m->tcpvars.ws = &m->tcpvars.tcp_opts[0];
     }
     /* FlowHandlePacket found or created the flow (ACL passed): flow.c:294-307.  Every packet of the stateless path
-     * is its flow's first, and FlowAdd orients the flow as that packet, so the direction is to-server. */
-    if (st == PPE_ST_ACL_FW) m->flags |= PKT_TO_SERVER | PKT_HAS_FLOW;
+     * is its flow's first, and FlowAdd orients the flow as that packet, so the direction is to-server.
+     * StreamTcp runs after that (flow.c:311-320), so a packet it drops carries the flags too. */
+    if (st == PPE_ST_ACL_FW || st >= PPE_ST_STREAM_RST_NO_SESSION) m->flags |= PKT_TO_SERVER | PKT_HAS_FLOW;
 }
 
 /* Classify `n` mbufs on the GPU (serialised) and fill their parse fields; returns PPE_OK or a PPE_E* code. */
@@ -419,9 +427,12 @@ static int classify_mbufs(mbuf_t **mb, uint32_t n) {
         r.acl_hit = hit;
         r.tuple = tuple;
         ppe_cfg_t cfg = {unsupport_proto_action ? 1u : 0u, syn_check ? 1u : 0u, 0};
+        const ppe_stream_tcp_cfg_t stcp = {stream_tcp_track_enable ? 1u : 0u, stream_tcp_midstream ? 1u : 0u,
+                                           stream_tcp_async_oneside ? 1u : 0u, 0u};
         pthread_mutex_lock(&g_ctx_lock);
         sync_running_locked();
-        rc = g_ctx ? ppe_classify_host(g_ctx, &b, &r, &cfg, 0) : PPE_ENODEV;
+        rc = g_ctx ? ppe_stream_tcp_set(g_ctx, &stcp) : PPE_ENODEV;
+        if (rc == PPE_OK) rc = ppe_classify_host(g_ctx, &b, &r, &cfg, 0);
         pthread_mutex_unlock(&g_ctx_lock);
         if (rc == PPE_OK)
             for (uint32_t i = 0; i < n; i++) fill_mbuf(mb[i], verdict[i], fh[i], hit[i], tuple + 4 * (size_t)i);

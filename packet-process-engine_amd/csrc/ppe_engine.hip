@@ -134,6 +134,8 @@ struct ppe_ctx {
     uint64_t stage_token = 0, tokens = 0;
     // counters
     unsigned long long *d_cslots = nullptr;
+    unsigned long long *d_sslots = nullptr;  // StreamTcp counter slots, [kSlotSets][max_grid][PPE_SSLOT_WORDS]
+    ppe_stream_tcp_cfg_t stcp = {0u, 0u, 0u, 0u};  // ppe_stream_tcp_set: off until set
     uint32_t max_grid = 0;
     // timing
     bool timing = false;
@@ -712,6 +714,9 @@ int launch(ppe_ctx *c, const ppe_batch_t *in, const ppe_result_t *out, uint32_t 
     a.off_rules = c->h_img[r][PPE_IMG_W_OFFRULES];
     a.off_resid = c->h_img[r][PPE_IMG_W_OFFRESID];
     a.cslots = c->d_cslots + (size_t)slot_set * c->max_grid * PPE_CSLOT_WORDS;
+    a.sslots = c->d_sslots + (size_t)slot_set * c->max_grid * PPE_SSLOT_WORDS;
+    a.stream = (c->stcp.track && !fl)
+                   ? PPE_STM_TRACK | ((c->stcp.midstream | c->stcp.async_oneside) ? PPE_STM_PICKUP : 0u) : 0u;
     if (fl) a.flow = *fl;
     if (grid_out) *grid_out = grid;
 
@@ -753,6 +758,10 @@ hipError_t use_device(ppe_ctx *c) {
 
 int check_batch(ppe_ctx *c, const ppe_batch_t *in, const ppe_cfg_t *cfg) {
     if (!in) return fail(c, PPE_EINVAL, "null batch");
+    // an ACK-only first packet with midstream pickup enters segment reassembly (stream-tcp.c:371-432): not built, and
+    // only syn_check keeps such packets from StreamTcp
+    if (c->stcp.track && c->stcp.midstream && cfg && cfg->syn_check == 0)
+        return fail(c, PPE_ENOTSUP, "stream tracking with midstream pickup needs syn_check (ACK-only pickup is not built)");
     if (in->n == 0) return PPE_OK;
     if (!in->hdr || !in->len) return fail(c, PPE_EINVAL, "hdr/len required");
     if (in->stride < 64 || in->stride > 256 || in->stride % 16u)
@@ -797,6 +806,10 @@ int ppe_ctx_create(int device, ppe_ctx_t **out) {
     int rc = PPE_OK;
     if (hipMalloc(&c->d_cslots, cs_bytes) != hipSuccess || hipMemset(c->d_cslots, 0, cs_bytes) != hipSuccess)
         rc = PPE_ENOMEM;
+    const size_t ss_bytes = (size_t)kSlotSets * c->max_grid * PPE_SSLOT_WORDS * sizeof(unsigned long long);
+    if (rc == PPE_OK &&
+        (hipMalloc(&c->d_sslots, ss_bytes) != hipSuccess || hipMemset(c->d_sslots, 0, ss_bytes) != hipSuccess))
+        rc = PPE_ENOMEM;
     for (int i = 0; i < 2 && rc == PPE_OK; ++i)
         if (hipEventCreateWithFlags(&c->img_done[i], hipEventDisableTiming) != hipSuccess) rc = PPE_EIO;
     // launch completions (struct Reader): pinned, device-mapped words and the device running counts
@@ -837,6 +850,7 @@ int ppe_ctx_destroy(ppe_ctx_t *c) {
         if (c->img_done[i]) (void)hipEventDestroy(c->img_done[i]);
     }
     if (c->d_cslots) (void)hipFree(c->d_cslots);
+    if (c->d_sslots) (void)hipFree(c->d_sslots);
     for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
     for (int i = 0; i < 2; ++i) {
         if (c->d_ring[i]) (void)hipFree(c->d_ring[i]);
@@ -1228,6 +1242,45 @@ int ppe_counters_clear(ppe_ctx_t *c) {
     return PPE_OK;
 }
 
+int ppe_stream_tcp_set(ppe_ctx_t *c, const ppe_stream_tcp_cfg_t *cfg) {
+    if (!c) return PPE_EINVAL;
+    const ppe_stream_tcp_cfg_t ref = {1u, 0u, 0u, 1u};  // stream-tcp.c:16-21
+    const ppe_stream_tcp_cfg_t v = cfg ? *cfg : ref;
+    if (v.track > 1 || v.midstream > 1 || v.async_oneside > 1 || v.reasm > 1)
+        return fail(c, PPE_EINVAL, "ppe_stream_tcp_set: every word must be 0/1");
+    c->stcp = v;  // by value into the kernel arguments of later launches
+    return PPE_OK;
+}
+
+int ppe_stream_tcp_get(ppe_ctx_t *c, ppe_stream_tcp_cfg_t *cfg) {
+    if (!c || !cfg) return PPE_EINVAL;
+    *cfg = c->stcp;
+    return PPE_OK;
+}
+
+int ppe_stream_counters_read(ppe_ctx_t *c, ppe_stream_counters_t *out) {
+    if (!c || !out) return PPE_EINVAL;
+    static_assert(PPE_SSLOT_WORDS == PPE_SC__COUNT && PPE_SC__COUNT <= 16, "stream counter slots");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipDeviceSynchronize());
+    const size_t words = (size_t)kSlotSets * c->max_grid * PPE_SSLOT_WORDS;
+    std::vector<unsigned long long> h(words);
+    HIPCHK(c, hipMemcpy(h.data(), c->d_sslots, words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    std::memset(out, 0, sizeof *out);
+    for (size_t b = 0; b < (size_t)kSlotSets * c->max_grid; ++b)
+        for (int i = 0; i < PPE_SSLOT_WORDS; ++i) out->c[i] += h[b * PPE_SSLOT_WORDS + i];
+    return PPE_OK;
+}
+
+int ppe_stream_counters_clear(ppe_ctx_t *c) {
+    if (!c) return PPE_EINVAL;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipDeviceSynchronize());
+    HIPCHK(c, hipMemset(c->d_sslots, 0,
+                        (size_t)kSlotSets * c->max_grid * PPE_SSLOT_WORDS * sizeof(unsigned long long)));
+    return PPE_OK;
+}
+
 int ppe_timing_enable(ppe_ctx_t *c, int on) {
     if (!c) return PPE_EINVAL;
     c->timing = on != 0;
@@ -1523,6 +1576,8 @@ int ppe_classify_flow(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *o
     if (!c || !out) return PPE_EINVAL;
     if (const int u = flow_usable(c)) return u;
     if (!out->verdict) return fail(c, PPE_EINVAL, "ppe_classify_flow needs the verdict output");
+    // later packets of a tracked flow need the TCP session state machine (stream-tcp.c:3005-3140): not built
+    if (c->stcp.track) return fail(c, PPE_ENOTSUP, "ppe_classify_flow with stream tracking on is not supported");
     int rc = check_batch(c, in, cfg);
     if (rc != PPE_OK || in->n == 0) return rc;
     FlowTable &t = *c->flow;

@@ -167,6 +167,9 @@ struct ppe_kargs {
     uint32_t off_leaf, off_rules, off_resid; /* image section offsets (words), from the image header: kernel arguments
                                                 (scalar registers, no load in the loop)                               */
     unsigned long long *cslots; /* [grid][PPE_CSLOT_WORDS] counter slots, one per workgroup */
+    unsigned long long *sslots; /* [grid][PPE_SSLOT_WORDS] StreamTcp counter slots (enum ppe_stream_counter) */
+    uint32_t stream;            /* StreamTcp first-packet verdict (ppe_stream_tcp_set): 0 = off, else PPE_STM_TRACK |
+                                   PPE_STM_PICKUP (midstream or async_oneside: SYN|ACK passes); wave-uniform */
     /* the launch's completion, for the host's image / descriptor-ring reader bookkeeping (no event marker behind each
        launch): every workgroup, at its end, adds 1 to *done_cnt (a per-slot running count); the one that brings it to
        done_target writes done_seq to *done_host (pinned host memory).  done_cnt NULL: not tracked */
@@ -208,6 +211,9 @@ struct ppe_tuple_kargs {
 };
 
 #define PPE_CSLOT_WORDS 32
+#define PPE_SSLOT_WORDS 8   /* PPE_SC__COUNT */
+#define PPE_STM_TRACK 1u
+#define PPE_STM_PICKUP 2u
 #define PPE_LDS_FIXED 1152u /* classify kernel LDS after the walk keys: 256 counter bins + 32 counters (u32) */
 #define PPE_BLOCK 256
 /* largest staged classifier image per workgroup (1024-thread workgroups, 2 per CU, each with 25 KB of keys + bins) */

@@ -12,6 +12,8 @@
  *   5. SoA verdict / hash / hit stores, wave-ballot compaction of FW/DROP indices per tile, and per-reason counters
  *      (one LDS add per packet into its (status, flags) bin, expanded once per workgroup into that workgroup's own
  *      counter slot — no contended global atomics).
+ *   4b. with StreamTcp tracking on (ppe_stream_tcp_set; the STM instantiations, csrc/ppe_kernels_stream.hip): the
+ *      first-packet verdict of StreamTcpPacketStateNone for the TCP packets the ACL forwarded, and its counters;
  * No MFMA: integer bitfield / compare work bound by HBM bandwidth and VALU issue.
  *
  * LDS layout of a workgroup (dynamic shared memory, nothing static):
@@ -134,11 +136,14 @@ __device__ __forceinline__ uint32_t reason_counter(uint32_t st) {
         ((uint64_t)PPE_C_IPV4_HEADERLEN_ERR << 35) | ((uint64_t)PPE_C_IPV4_VERSION_ERR << 40) |
         ((uint64_t)PPE_C_IPV4_PKTLEN_ERR << 45) | ((uint64_t)PPE_C_FRAG_FRAGLEN_ERR << 50) |
         ((uint64_t)PPE_C_FRAG_PUNT << 55);
-    constexpr uint64_t K1 =  // st 12..19
+    constexpr uint64_t K1 =  // st 12..23 (the StreamTcp drops 20..23: the ACL forwarded them, STAT_ACL_FW flow.c:240)
         ((uint64_t)PPE_C_IPV4_UNSUPPORT << 0) | ((uint64_t)PPE_C_UDP_HEADERLEN_ERR << 5) |
         ((uint64_t)PPE_C_UDP_PKTLEN_ERR << 10) | ((uint64_t)PPE_C_TCP_HEADERLEN_ERR << 15) |
         ((uint64_t)PPE_C_TCP_PKTLEN_ERR << 20) | ((uint64_t)PPE_C_FLOW_TCP_NO_SYN_FIRST << 25) |
-        ((uint64_t)PPE_C_WINDOW_PUNT << 30) | ((uint64_t)PPE_C_FLOW_NODE_NOMEM << 35);
+        ((uint64_t)PPE_C_WINDOW_PUNT << 30) | ((uint64_t)PPE_C_FLOW_NODE_NOMEM << 35) |
+        ((uint64_t)PPE_C_ACL_FW << 40) | ((uint64_t)PPE_C_ACL_FW << 45) | ((uint64_t)PPE_C_ACL_FW << 50) |
+        ((uint64_t)PPE_C_ACL_FW << 55);
+    static_assert(PPE_ST__COUNT == 24, "reason table covers statuses 0..23");
     const bool lo = st < 12u;
     return (uint32_t)(((lo ? K0 : K1) >> (5u * (lo ? st : st - 12u))) & 31u);
 }
@@ -155,6 +160,20 @@ __device__ __forceinline__ void ld_l4_sync(const uint8_t *q, uint32_t &a, uint32
         : "=&v"(a), "=&v"(b), "=&v"(c), "=&v"(d)
         : "v"(q)
         : "memory");
+}
+// th_ack (TCP header bytes 8-11) behind IPv4 options, as two halves (the header is only 2-byte aligned): their OR,
+// for the non-zero test of StreamTcp's broken-ack counter.  Inside the window whenever the TCP header's first 14
+// bytes are (the caller's win_short check).
+__device__ __forceinline__ uint32_t ld_ack_sync(const uint8_t *q) {
+    uint32_t a, b;
+    asm volatile(
+        "global_load_ushort %0, %2, off offset:8\n\t"
+        "global_load_ushort %1, %2, off offset:10\n\t"
+        "s_waitcnt vmcnt(0)"
+        : "=&v"(a), "=&v"(b)
+        : "v"(q)
+        : "memory");
+    return a | b;
 }
 __device__ __forceinline__ void ld_mac_sync(const uint8_t *q, uint32_t &a, uint32_t &b, uint32_t &c) {
     typedef uint32_t v3u __attribute__((ext_vector_type(3)));
@@ -258,14 +277,16 @@ __device__ __forceinline__ uint32_t bin_counters(uint32_t key, uint64_t act_tabl
     if (vl && st != PPE_ST_VLAN_UNSUPPORT) cb |= CB(PPE_C_VLAN_RX_OK);
     const bool l4_in = st == PPE_ST_ACL_FW || st == PPE_ST_ACL_DROP || st == PPE_ST_UDP_HEADER_ERR ||
                        st == PPE_ST_UDP_LEN_ERR || st == PPE_ST_TCP_HEADER_ERR || st == PPE_ST_TCP_LEN_ERR ||
-                       st == PPE_ST_FLOW_TCP_NO_SYN_FIRST || st == PPE_ST_WINDOW_PUNT || st == PPE_ST_FLOW_NOMEM;
+                       st == PPE_ST_FLOW_TCP_NO_SYN_FIRST || st == PPE_ST_WINDOW_PUNT || st == PPE_ST_FLOW_NOMEM ||
+                       st >= PPE_ST_STREAM_RST_NO_SESSION;
     if (l4_in) cb |= CB(PPE_C_IPV4_RX_OK);
     if (l4 && !tcp) cb |= CB(PPE_C_UDP_RX_OK);
     if (tcp) cb |= CB(PPE_C_TCP_RX_OK);
     if (st == PPE_ST_FLOW_TCP_NO_SYN_FIRST || st == PPE_ST_ACL_DROP || st == PPE_ST_FLOW_NOMEM)
         cb |= CB(PPE_C_FLOW_PROC_FAIL);
     if (st == PPE_ST_FLOW_NOMEM) cb |= CB(PPE_C_ACL_FW);  // counted before FlowAdd failed (flow.c:240)
-    if (st == PPE_ST_ACL_FW) cb |= CB(PPE_C_FLOW_PROC_OK);
+    // (a StreamTcp drop: FlowHandlePacket had returned OK, STAT_FLOW_PROC_OK flow.c:309, before StreamTcp ran)
+    if (st == PPE_ST_ACL_FW || st >= PPE_ST_STREAM_RST_NO_SESSION) cb |= CB(PPE_C_FLOW_PROC_OK);
     const uint32_t act = (uint32_t)(act_table >> (2u * st)) & 3u;
     cb |= act == PPE_ACT_FW ? CB(PPE_C_OUT_FW) : (act == PPE_ACT_DROP ? CB(PPE_C_OUT_DROP) : CB(PPE_C_OUT_PUNT));
     return cb;
@@ -276,6 +297,27 @@ struct Dec {
     uint32_t sip, dip, sport, dport, proto, paylen;
     uint32_t tcpopt;  // TCP with options: window byte offset of the TCP header | option bytes << 8 | avail << 16
 };
+// StreamTcp tracking on (ppe_kargs.stream): Dec.flags carries, above the 16 verdict flag bits (every store of the flags
+// shifts or masks them away), sf = th_flags & (FIN | SYN | RST | ACK) | PPE_SF_BROKEN_ACK: no register of its own
+// across the ACL walk, and in the multi-tile key's meta word (flags << 8) it lands in the free bits 24-29
+#define PPE_SF_SHIFT 16u
+#define PPE_SF_BROKEN_ACK 0x20u  // ACK clear and a non-zero th_ack (stream-tcp.c:3000)
+
+// StreamTcpPacketStateNone (dataplane/src/plugin/stream-tcp/stream-tcp.c:237-441) for a TCP packet the ACL forwarded:
+// the first matching branch of the reference decides, so the branches are applied in reverse order.  sf as above,
+// stm = ppe_kargs.stream.  An ACK-only packet with midstream on never gets here (the host refuses that setting
+// without syn_check, and syn_check stops the packet before the ACL).
+__device__ __forceinline__ __attribute__((unused)) uint32_t stream_tcp_none(uint32_t sf, uint32_t stm) {
+    uint32_t s = (sf & 0x10u) ? (uint32_t)PPE_ST_STREAM_MIDSTREAM_OFF : (uint32_t)PPE_ST_ACL_FW;  // :364-370, :434-437
+    s = (sf & 0x02u) ? (uint32_t)PPE_ST_ACL_FW : s;                                                // SYN, :296-362
+    s = (sf & 0x12u) == 0x12u                                                                       // SYN|ACK, :255-261
+            ? ((stm & PPE_STM_PICKUP) ? (uint32_t)PPE_ST_ACL_FW : (uint32_t)PPE_ST_STREAM_MIDSTREAM_ONESIDE_OFF) : s;
+    s = (sf & 0x01u) ? (uint32_t)PPE_ST_STREAM_FIN_NO_SESSION : s;                                  // FIN, :249-254
+    s = (sf & 0x04u) ? (uint32_t)PPE_ST_STREAM_RST_NO_SESSION : s;                                  // RST, :243-248
+    return s;
+}
+// the bins (status 24..27, flags 0: no such status) that hold a workgroup's StreamTcp count-first counters
+#define PPE_STREAM_BIN0 24u
 
 // Decode of one packet, straight-line: every check of the reference is evaluated, then the terminal status is
 // chosen by applying the checks in REVERSE order of the reference's control flow, so the first failing check
@@ -285,7 +327,7 @@ struct Dec {
 // for Defrag instead (decode-ipv4.c:106-109): ip_id, the fragment offset in bytes and frag_len (ppe_hip.h tuple).
 template <bool TUP = true>
 __device__ __forceinline__ Dec decode(const uint32_t (&w)[13], uint32_t len32, const uint8_t *hdr, uint32_t p,
-                                      uint32_t stride, uint32_t syn_check) {
+                                      uint32_t stride, uint32_t syn_check, uint32_t stm = 0u) {
     Dec k;
     const uint32_t len = len32 & 0xffffu;  // Decode passes (uint16_t)pkt_totallen, decode.c:22
     // ---- Ethernet: dataplane/src/decode/decode-ethernet.c:23-115 ----
@@ -331,12 +373,14 @@ __device__ __forceinline__ Dec decode(const uint32_t (&w)[13], uint32_t len32, c
     const bool win_short = !fast & (l4off + (is_tcp ? 14u : 6u) > stride);
     uint32_t sport = be16_hi(D[5]), dport = be16_lo(D[6]);
     uint32_t x = is_tcp ? (D[8] >> 16) : be16_hi(D[6]);  // TCP: offx2 | flags << 8;  UDP: uh_len
+    uint32_t ackw = (D[7] >> 16) | (D[8] & 0xffffu);     // TCP th_ack, L4+8..11 (only tested for non-zero, stm)
     if (l4_in & !fast & !win_short) {  // IPv4 options: L4 header at a data-dependent offset
         uint32_t h0, h1, h2, h6;
         ld_l4_sync(hdr + (size_t)p * stride + l4off, h0, h1, h2, h6);
         sport = bswap16(h0);
         dport = bswap16(h1);
         x = is_tcp ? h6 : bswap16(h2);
+        if (stm && is_tcp) ackw = ld_ack_sync(hdr + (size_t)p * stride + l4off);
     }
     // ---- UDP: dataplane/src/decode/decode-udp.c:16-49;  TCP: dataplane/src/decode/decode-tcp.c:135-190 ----
     const uint32_t thl = ((x & 0xffu) >> 4) << 2;  // uint8_t hlen, decode-tcp.c:148
@@ -371,6 +415,10 @@ __device__ __forceinline__ Dec decode(const uint32_t (&w)[13], uint32_t len32, c
     k.flags = ((l2_ok & is_vl & (vlen >= 4u)) ? PPE_F_VLAN : 0u) | (l4_ok ? PPE_F_L4 : 0u) |
               ((l4_ok & is_tcp) ? PPE_F_TCP : 0u) | ((l4_ok & is_tcp & syn) ? PPE_F_SYN : 0u) |
               ((ip_ok & frag) ? PPE_F_FRAG : 0u);
+    if (stm) {  // wave-uniform (kernel argument): the flag bits StreamTcp looks at, for finish()
+        const uint32_t F = (x >> 8) & 0x17u;  // TH_FIN 0x01, TH_SYN 0x02, TH_RST 0x04, TH_ACK 0x10
+        k.flags |= (F | ((((F & 0x10u) == 0u) & (ackw != 0u)) ? PPE_SF_BROKEN_ACK : 0u)) << PPE_SF_SHIFT;
+    }
     // zeroed by masks, not selects: ROCm 7.2 miscompiles the select form (dport zeroed for NO_SYN packets;
     // profiles/r3_select_miscompile.md, tools/repro_select_miscompile.sh)
     const uint32_t ipm = ip_ok ? ~0u : 0u, l4m = l4_ok ? ~0u : 0u;
@@ -1263,7 +1311,10 @@ __device__ __forceinline__ uint32_t flow_find_claim(const ppe_flowdev &f, const 
 #ifndef PPE_CUT_SPLIT_WAVES  // the same for split images (entries from L2)
 #define PPE_CUT_SPLIT_WAVES PPE_WAVES_PER_EU
 #endif
-template <int MODE, int PF, int BLOCK, bool FLOW, bool PART = false>
+// STM: StreamTcp's first-packet verdict (ppe_stream_tcp_set tracking on; stateless kernels only).  A template
+// parameter, not a run-time branch: the 64-VGPR kernels have no register to spare (as a uniform branch the check
+// cost C1's kernel 2 spilled VGPRs with tracking off), so with tracking off the kernels contain none of it.
+template <int MODE, int PF, int BLOCK, bool FLOW, bool PART = false, bool STM = false>
 __global__ __launch_bounds__(BLOCK, (PF == PF_MULTI && !FLOW) ? PPE_MT_WAVES
                                     : FLOW                                       ? PPE_FLOW_WAVES
                                     : (PF == PF_CUT && MODE == IMG_LDS)          ? PPE_CUT_LDS_WAVES
@@ -1278,6 +1329,8 @@ void ppe_classify_kernel(ppe_kargs a) {
     constexpr int MT = FLOW ? 1 : PF == PF_MULTI ? (MODE == IMG_LDS ? PPE_MT_LDS : PPE_MT) : 1;
     constexpr bool CUT = PF == PF_CUT && !FLOW;
     constexpr bool KEYS = MT == 1 && !CUT;  // node walks: per-wave key slots in LDS
+    static_assert(!(STM && FLOW), "stream tracking: stateless kernels only");
+    const uint32_t stm = STM ? a.stream : 0u;
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     using L = Lds<BLOCK, KEYS, FLOW ? 4u * PPE_UPD_OWNERS * (1u + (PPE_UPD_LDS ? PPE_UPD_CAP : 0u)) : 0u>;
     uint32_t *bins = smem + L::BINS / 4u;    // [PPE_NBINS] packets per (status, flags) bin of this workgroup
@@ -1362,8 +1415,26 @@ void ppe_classify_kernel(ppe_kargs a) {
     unsigned long long rx_bytes = 0;  // STAT_RECV_PB_ADD (oct-rxtx.c:213) of this lane's packets
 
     // after the ACL: verdict / hash / hit stores, FLOW pending records, compaction, counters
-    auto finish = [&](uint32_t tile, uint32_t p, bool valid, const Dec &k, uint32_t fh, int32_t hit, bool pend) {
-        const uint32_t st = k.st;
+    // (sfw >> PPE_SF_SHIFT = the packet's StreamTcp flag bits, read only with tracking on)
+    auto finish = [&](uint32_t tile, uint32_t p, bool valid, const Dec &k, uint32_t fh, int32_t hit, bool pend,
+                      uint32_t sfw) {
+        uint32_t st = k.st;
+        if constexpr (STM) {
+            // StreamTcp (flow.c:311-320) for the TCP packets the ACL forwarded, each the first of its flow: the
+            // counters of stream-tcp.c:2989-3003 (wave ballots, one LDS add per tile and counter), then the verdict
+            const bool trk = valid && st == PPE_ST_ACL_FW &&
+                             (k.flags & (PPE_F_TCP | PPE_F_ACL)) == (PPE_F_TCP | PPE_F_ACL);
+            const uint32_t sf = sfw >> PPE_SF_SHIFT;
+            if (!(PPE_ABLATE & 2)) {
+                const uint64_t b0 = __builtin_amdgcn_ballot_w64(trk && (sf & 0x12u) == 0x12u);  // SYN_ACK_COUNT
+                const uint64_t b1 = __builtin_amdgcn_ballot_w64(trk && (sf & 0x12u) == 0x02u);  // else SYN_COUNT
+                const uint64_t b2 = __builtin_amdgcn_ballot_w64(trk && (sf & 0x04u) != 0u);     // RST_COUNT
+                const uint64_t b3 = __builtin_amdgcn_ballot_w64(trk && (sf & PPE_SF_BROKEN_ACK) != 0u);
+                const uint32_t c = (uint32_t)__popcll(lane == 0u ? b0 : lane == 1u ? b1 : lane == 2u ? b2 : b3);
+                if (lane < 4u && c) atomicAdd(&bins[PPE_STREAM_BIN0 + lane], c);
+            }
+            st = trk ? stream_tcp_none(sf, stm) : st;
+        }
         const uint32_t act = (uint32_t)(act_table >> (2u * st)) & 3u;
         const uint32_t po = 4u * p;  // byte offset of this packet's SoA output words
         if (valid && !FLOW && (B.flags & PPE_BD_PACKED)) {
@@ -1434,7 +1505,7 @@ void ppe_classify_kernel(ppe_kargs a) {
         const uint32_t p = (tile << 6) + lane;
         const bool valid = p < B.n;
         if (!(PPE_ABLATE & 2) && valid) rx_bytes += wlen;
-        Dec k = decode<!PART>(w, wlen, B.hdr, p, B.stride, a.syn_check);
+        Dec k = decode<!PART>(w, wlen, B.hdr, p, B.stride, a.syn_check, stm);
 
         uint32_t fh = 0;
         int32_t hit = -1;
@@ -1476,10 +1547,11 @@ void ppe_classify_kernel(ppe_kargs a) {
             k.st = drop ? (uint32_t)PPE_ST_ACL_DROP : (uint32_t)PPE_ST_ACL_FW;
             k.flags |= PPE_F_ACL;
         }
-        finish(tile, p, valid, k, fh, hit, pend);
+        finish(tile, p, valid, k, fh, hit, pend, k.flags);
     };
 
-    // multi-tile rounds: per tile the packed key (sip, dip, ports, meta = status | flags << 8 | proto << 16) and, for
+    // multi-tile rounds: per tile the packed key (sip, dip, ports, meta = status | flags << 8 | proto << 16, the
+    // StreamTcp flag bits of Dec.flags landing in bits 24-29) and, for
     // the tuple output only, payload length and TCP option word; the flow hash is computed after the walk (fewer live
     // registers while the block reads are in flight)
     auto mt_decode = [&](uint32_t t0, const uint4 (&r0)[MT], const uint4 (&r1)[MT], const uint4 (&r2)[MT],
@@ -1491,7 +1563,7 @@ void ppe_classify_kernel(ppe_kargs a) {
             if (p < B.n) rx_bytes += rl[t];
             const uint32_t w[13] = {r0[t].x, r0[t].y, r0[t].z, r0[t].w, r1[t].x, r1[t].y, r1[t].z, r1[t].w,
                                     r2[t].x, r2[t].y, r2[t].z, r2[t].w, r3[t]};
-            Dec d = decode<!PART>(w, rl[t], B.hdr, p, B.stride, a.syn_check);
+            Dec d = decode<!PART>(w, rl[t], B.hdr, p, B.stride, a.syn_check, stm);
             if ((PPE_ABLATE & 1) && d.st == ST_ACL) {
                 d.st = PPE_ST_ACL_FW;
                 d.flags |= PPE_F_ACL;
@@ -1516,7 +1588,7 @@ void ppe_classify_kernel(ppe_kargs a) {
         k.dport = key[2] >> 16;
         k.st = key[3] & 0xffu;
         k.flags = (key[3] >> 8) & 0xffu;
-        k.proto = key[3] >> 16;
+        k.proto = (key[3] >> 16) & 0xffu;
         k.paylen = kpay;
         k.tcpopt = kopt;
         const uint32_t fh = (!(PPE_ABLATE & 8) && (k.flags & PPE_F_L4))
@@ -1525,15 +1597,15 @@ void ppe_classify_kernel(ppe_kargs a) {
             k.st = drop ? (uint32_t)PPE_ST_ACL_DROP : (uint32_t)PPE_ST_ACL_FW;
             k.flags |= PPE_F_ACL;
         }
-        finish(tile, p, p < B.n, k, fh, need ? hit : -1, false);
+        finish(tile, p, p < B.n, k, fh, need ? hit : -1, false, key[3] >> 8);
     };
     // a leaf's rule check (non-compact images: leaf lists / residual fields, rare)
     auto mt_leaf = [&](uint32_t tile, const uint32_t (&key)[4], const uint4 &nd, int32_t &hit, bool &drop) {
         uint32_t rule_act;
         const uint32_t p = (tile << 6) + lane;
         const MacFromWindow mac = {B.hdr, p, B.stride};
-        acl_leaf<MODE, L::IMGB>(a.img, geo, nd, key[0], key[1], key[2] & 0xffffu, key[2] >> 16, key[3] >> 16, mac,
-                                B.ts, p, a.now, hit, rule_act);
+        acl_leaf<MODE, L::IMGB>(a.img, geo, nd, key[0], key[1], key[2] & 0xffffu, key[2] >> 16,
+                                (key[3] >> 16) & 0xffu, mac, B.ts, p, a.now, hit, rule_act);
         drop = rule_act == ACL_RULE_ACTION_DROP;
     };
 
@@ -1603,7 +1675,7 @@ void ppe_classify_kernel(ppe_kargs a) {
                 if (need[t]) {
                     if (geo.off_crec)
                         acl_leaf_compact<L::IMGB>(a.img, geo, nd[t].z, key[t][0], key[t][1], key[t][2] & 0xffffu,
-                                                  key[t][2] >> 16, (key[t][3] >> 16) == 6u, hit[t], drop[t]);
+                                                  key[t][2] >> 16, ((key[t][3] >> 16) & 0xffu) == 6u, hit[t], drop[t]);
                     else
                         mt_leaf(t0 + t, key[t], nd[t], hit[t], drop[t]);
                 }
@@ -1658,7 +1730,7 @@ void ppe_classify_kernel(ppe_kargs a) {
                     if (need[t]) {
                         const uint32_t sip = key[t][0], dip = key[t][1], sport = key[t][2] & 0xffffu,
                                        dport = key[t][2] >> 16;
-                        const bool tcp = (key[t][3] >> 16) == 6u;
+                        const bool tcp = ((key[t][3] >> 16) & 0xffu) == 6u;
                         if (RPF && geo.off_crec)
                             crec_check<L::IMGB>(a.img, geo, nd[t].z, rcur, sip, dip, sport, dport, tcp, hit, drop);
                         else if (geo.off_crec)
@@ -1691,6 +1763,18 @@ void ppe_classify_kernel(ppe_kargs a) {
     for (uint32_t b = tid; b < PPE_NBINS; b += BLOCK) {  // expand the bins into counter increments
         const uint32_t c = bins[b];
         if (c) {
+            if (STM && (b & 31u) >= PPE_ST_STREAM_RST_NO_SESSION) {
+                // StreamTcp tracking: this workgroup's counts into its own stream counter slot (uncontended), one add
+                // per non-empty bin: the count-first accumulators, and each drop's reason (its status bins)
+                const uint32_t st = b & 31u;
+                const uint32_t sc =
+                    st < PPE_ST__COUNT ? (uint32_t)PPE_SC_RST_BUT_NO_SESSION + st - PPE_ST_STREAM_RST_NO_SESSION
+                    : (b & 3u) == 3u   ? (uint32_t)PPE_SC_PKT_BROKEN_ACK  // (bins PPE_STREAM_BIN0 + 0..3)
+                                       : (uint32_t)PPE_SC_SYN_ACK_COUNT + (b & 3u);
+                __hip_atomic_fetch_add(&a.sslots[(size_t)blockIdx.x * PPE_SSLOT_WORDS + sc], (unsigned long long)c,
+                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (st >= PPE_ST__COUNT) continue;
+            }
             for (uint32_t cb = bin_counters(b, act_table); cb; cb &= cb - 1u) atomicAdd(&lcnt[__builtin_ctz(cb)], c);
         }
     }
@@ -2302,7 +2386,51 @@ __global__ __launch_bounds__(PPE_BLOCK) void ppe_acl_tuple_kernel(ppe_tuple_karg
 
 }  // namespace
 
-#ifdef PPE_TU_HOIST
+#define PPE_DISPATCH_B(FN, M, P, ...)                                \
+    do {                                                             \
+        if (block == 1024) return FN<M, P, 1024>(__VA_ARGS__);       \
+        if (block == 512) return FN<M, P, 512>(__VA_ARGS__);         \
+        return FN<M, P, 256>(__VA_ARGS__);                           \
+    } while (0)
+#define PPE_DISPATCH_P(FN, M, ...)                                   \
+    do {                                                             \
+        if (pipe == PF_NONE) PPE_DISPATCH_B(FN, M, PF_NONE, __VA_ARGS__); \
+        if (pipe == PF_MULTI) PPE_DISPATCH_B(FN, M, PF_MULTI, __VA_ARGS__); \
+        if (pipe == PF_CUT) PPE_DISPATCH_B(FN, M, PF_CUT, __VA_ARGS__); \
+        PPE_DISPATCH_B(FN, M, PF_HOIST, __VA_ARGS__);                \
+    } while (0)
+#define PPE_DISPATCH(FN, ...)                                        \
+    do {                                                             \
+        if (mode == IMG_LDS) PPE_DISPATCH_P(FN, IMG_LDS, __VA_ARGS__);     \
+        if (mode == IMG_SPLIT) PPE_DISPATCH_P(FN, IMG_SPLIT, __VA_ARGS__); \
+        PPE_DISPATCH_P(FN, IMG_GLOBAL, __VA_ARGS__);                 \
+    } while (0)
+
+#if defined(PPE_TU_STREAM)
+// csrc/ppe_kernels_stream.hip: this file again, exporting only the stateless kernels with StreamTcp's verdict (STM)
+template <int M, int P, int B>
+static int launch_stream_t(const ppe_kargs *a, uint32_t grid, size_t shmem, hipStream_t s, hipEvent_t e0,
+                           hipEvent_t e1) {
+    if constexpr (P != PF_NONE) {  // (the throughput-layout variants exist for the same fetch modes as without STM)
+        if (a->part_layout)
+            hipExtLaunchKernelGGL((ppe_classify_kernel<M, P, B, false, true, true>), dim3(grid), dim3(B), shmem, s, e0,
+                                  e1, 0, *a);
+        else
+            hipExtLaunchKernelGGL((ppe_classify_kernel<M, P, B, false, false, true>), dim3(grid), dim3(B), shmem, s, e0,
+                                  e1, 0, *a);
+    } else {
+        hipExtLaunchKernelGGL((ppe_classify_kernel<M, P, B, false, false, true>), dim3(grid), dim3(B), shmem, s, e0, e1,
+                              0, *a);
+    }
+    return (int)hipGetLastError();
+}
+extern "C" int ppe_launch_classify_stream(const ppe_kargs *a, uint32_t grid, size_t shmem, int mode, int pipe,
+                                          int block, void *stream, void *ev_start, void *ev_stop) {
+    const hipStream_t s = (hipStream_t)stream;
+    const hipEvent_t e0 = (hipEvent_t)ev_start, e1 = (hipEvent_t)ev_stop;
+    PPE_DISPATCH(launch_stream_t, a, grid, shmem, s, e0, e1);
+}
+#elif defined(PPE_TU_HOIST)
 // csrc/ppe_kernels_hoist.hip: this file again, built with LLVM's iterative-ILP machine scheduler, exporting only the
 // stateless hoisted-fetch kernels over an LDS-resident image (C1's variant: kernel −2 %, r6s; the cut-list and split
 // variants are slower under it and stay in the default build, profiles/r6_ab_runs.md r6j / r6s)
@@ -2341,6 +2469,8 @@ extern "C" int ppe_occupancy_hoist_lds(size_t shmem, int block) {
 extern "C" int ppe_launch_classify_hoist_lds(const ppe_kargs *a, uint32_t grid, size_t shmem, int block, void *stream,
                                              void *ev_start, void *ev_stop);
 extern "C" int ppe_occupancy_hoist_lds(size_t shmem, int block);
+extern "C" int ppe_launch_classify_stream(const ppe_kargs *a, uint32_t grid, size_t shmem, int mode, int pipe,
+                                          int block, void *stream, void *ev_start, void *ev_stop);
 
 template <int M, int P, int B>
 static int launch_t(const ppe_kargs *a, uint32_t grid, size_t shmem, hipStream_t s, hipEvent_t e0, hipEvent_t e1,
@@ -2385,29 +2515,13 @@ static size_t classify_shmem(uint32_t lds_words, int mode, int pipe, int block, 
     return base + (((size_t)lds_words * 4u + 1023u) & ~(size_t)1023u);
 }
 
-#define PPE_DISPATCH_B(FN, M, P, ...)                                \
-    do {                                                             \
-        if (block == 1024) return FN<M, P, 1024>(__VA_ARGS__);       \
-        if (block == 512) return FN<M, P, 512>(__VA_ARGS__);         \
-        return FN<M, P, 256>(__VA_ARGS__);                           \
-    } while (0)
-#define PPE_DISPATCH_P(FN, M, ...)                                   \
-    do {                                                             \
-        if (pipe == PF_NONE) PPE_DISPATCH_B(FN, M, PF_NONE, __VA_ARGS__); \
-        if (pipe == PF_MULTI) PPE_DISPATCH_B(FN, M, PF_MULTI, __VA_ARGS__); \
-        if (pipe == PF_CUT) PPE_DISPATCH_B(FN, M, PF_CUT, __VA_ARGS__); \
-        PPE_DISPATCH_B(FN, M, PF_HOIST, __VA_ARGS__);                \
-    } while (0)
-#define PPE_DISPATCH(FN, ...)                                        \
-    do {                                                             \
-        if (mode == IMG_LDS) PPE_DISPATCH_P(FN, IMG_LDS, __VA_ARGS__);     \
-        if (mode == IMG_SPLIT) PPE_DISPATCH_P(FN, IMG_SPLIT, __VA_ARGS__); \
-        PPE_DISPATCH_P(FN, IMG_GLOBAL, __VA_ARGS__);                 \
-    } while (0)
-
 extern "C" int ppe_launch_classify(const ppe_kargs *a, uint32_t grid, int mode, int pipe, int block, int flow,
                                    void *stream, void *ev_start, void *ev_stop) {
     const size_t shmem = classify_shmem(a->stage_words, mode, pipe, block, flow != 0);
+    // StreamTcp tracking on: the same kernel with the verdict compiled in (same launch bounds and LDS, so the same
+    // occupancy and grid), from its own translation unit
+    if (a->stream && !flow)
+        return ppe_launch_classify_stream(a, grid, shmem, mode, pipe, block, stream, ev_start, ev_stop);
     hipStream_t s = (hipStream_t)stream;
     hipEvent_t e0 = (hipEvent_t)ev_start, e1 = (hipEvent_t)ev_stop;
     PPE_DISPATCH(launch_t, a, grid, shmem, s, e0, e1, flow);

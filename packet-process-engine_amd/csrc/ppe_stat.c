@@ -133,6 +133,50 @@ int ppe_format_pkt_stat_ex(const ppe_counters_t *c, const ppe_defrag_info_t *df,
     return (int)o.len;
 }
 
+/* `show tcpstream statistic` (dp_show_tcpstream_stat, dp_cmd.c:174-842): the tcpstreamtrackstat lines, then the
+ * tcpstreamreasmstat lines, in the reference's order.  The stateless path produces the six counters with a source
+ * below (the two *_DISABLE drop reasons are counted, ppe_stream_counters_t, but the reference prints no line for
+ * them); the session state machine's and the reassembly's lines print 0. */
+static const stat_line_t k_tcpstream[] = {
+    {"SYN_ACK_COUNT", PPE_SC_SYN_ACK_COUNT}, {"SYN_COUNT", PPE_SC_SYN_COUNT}, {"RST_COUNT", PPE_SC_RST_COUNT},
+    {"RST_BUT_NO_SESSION", PPE_SC_RST_BUT_NO_SESSION}, {"FIN_BUT_NO_SESSION", PPE_SC_FIN_BUT_NO_SESSION},
+    {"SESSION_NO_MEM", NONE}, {"FIN_INVALID_ACK", NONE}, {"FIN_OUT_OF_WINDOW", NONE}, {"SESSION_PARAM_ERR", NONE},
+    {"WHS3_SYNACK_TOSERVER_SYN_RECV", NONE}, {"WHS3_SYNACK_SEQ_MISMATCH", NONE},
+    {"WHS3_SYNACK_RESEND_WITH_DIFFERENT_ACK", NONE}, {"WHS3_SYN_TOCLIENT_ON_SYN_RECV", NONE},
+    {"WHS3_SYN_RESEND_DIFF_SEQ_ON_SYN_RECV", NONE}, {"WHS3_SYNACK_IN_WRONG_DIRECTION", NONE},
+    {"WHS3_ACK_IN_WRONG_DIR", NONE}, {"WHS3_RIGHT_SEQ_WRONG_ACK_EVASION", NONE}, {"WHS3_WRONG_SEQ_WRONG_ACK", NONE},
+    {"WHS3_ASYNC_WRONG_SEQ", NONE}, {"WHS3_SYNACK_WITH_WRONG_ACK", NONE}, {"WHS4_WRONG_SEQ", NONE},
+    {"WHS4_INVALID_ACK", NONE}, {"WHS4_SYNACK_WITH_WRONG_ACK", NONE}, {"WHS4_SYNACK_WITH_WRONG_SYN", NONE},
+    {"EST_INVALID_ACK", NONE}, {"EST_PKT_BEFORE_LAST_ACK", NONE}, {"EST_PACKET_OUT_OF_WINDOW", NONE},
+    {"EST_SYNACK_RESEND", NONE}, {"EST_SYNACK_TOSERVER", NONE}, {"EST_SYNACK_RESEND_WITH_DIFFERENT_ACK", NONE},
+    {"EST_SYNACK_RESEND_WITH_DIFF_SEQ", NONE}, {"EST_SYN_TOCLIENT", NONE}, {"EST_SYN_RESEND_DIFF_SEQ", NONE},
+    {"EST_SYN_RESEND", NONE}, {"PKT_RETRANSMISSION", NONE}, {"FIN2_FIN_WRONG_SEQ", NONE}, {"FIN2_INVALID_ACK", NONE},
+    {"FIN2_ACK_WRONG_SEQ", NONE}, {"FIN1_FIN_WRONG_SEQ", NONE}, {"FIN1_INVALID_ACK", NONE},
+    {"FIN1_ACK_WRONG_SEQ", NONE}, {"SHUTDOWN_SYN_RESEND", NONE}, {"CLOSEWAIT_FIN_OUT_OF_WINDOW", NONE},
+    {"CLOSING_ACK_WRONG_SEQ", NONE}, {"CLOSEWAIT_INVALID_ACK", NONE}, {"CLOSING_INVALID_ACK", NONE},
+    {"CLOSEWAIT_PKT_BEFORE_LAST_ACK", NONE}, {"CLOSEWAIT_ACK_OUT_OF_WINDOW", NONE}, {"LASTACK_ACK_WRONG_SEQ", NONE},
+    {"LASTACK_INVALID_ACK", NONE}, {"TIMEWAIT_ACK_WRONG_SEQ", NONE}, {"TIMEWAIT_INVALID_ACK", NONE},
+    {"PKT_INVALID_ACK", NONE}, {"PKT_BAD_WINDOW_UPDATE", NONE}, {"PKT_BROKEN_ACK", PPE_SC_PKT_BROKEN_ACK},
+    {"REASM_BEFORE_RA_BASE", NONE}, {"REASM_SEG_NO_MEM", NONE}, {"REASM_HW2SW_ERR", NONE}, {"REASM_CACHE", NONE},
+    {"REASM_NO_NEED_REASM", NONE}, {"REASM_SETUP_FAIL", NONE}, {"REASM_OK", NONE}, {"REASM_OVERLAP", NONE}};
+
+int ppe_format_tcpstream_stat(const ppe_stream_counters_t *c, const ppe_stream_tcp_cfg_t *cfg, char *buf, size_t cap) {
+    if (!c) return PPE_EINVAL;
+    out_t o = {buf, buf ? cap : 0, 0};
+    if (buf && cap) buf[0] = 0;
+    put(&o, "tcpstream statistic:\n");
+    put(&o, "tcpstream track: %s\n", cfg && cfg->track ? "enable" : "disable");
+    put(&o, "tcpstream reasm: %s\n", cfg && cfg->reasm ? "enable" : "disable");
+    put(&o, "----------------------------------\n");
+    for (size_t i = 0; i < sizeof k_tcpstream / sizeof k_tcpstream[0]; i++) {
+        const int ci = k_tcpstream[i].counter;
+        put(&o, "%s: %ld\n", k_tcpstream[i].name, ci == NONE ? 0L : (long)c->c[ci]);
+    }
+    put(&o, "----------------\n");
+    put(&o, "\n");
+    return (int)o.len;
+}
+
 int ppe_format_flow_stat(const ppe_flow_info_t *f, char *buf, size_t cap) {
     return ppe_format_flow_stat_ex(f, NULL, buf, cap);
 }

@@ -20,8 +20,15 @@ PPE_OK = 0
 ST = dict(ACL_FW=0, ACL_DROP=1, L2_HEADER_ERR=2, L2_UNSUPPORT=3, VLAN_HEADER_ERR=4, VLAN_LAYER_EXCEED=5,
           VLAN_UNSUPPORT=6, IPV4_HEADER_ERR=7, IPV4_VERSION_ERR=8, IPV4_LEN_ERR=9, FRAG_LEN_ERR=10, FRAG=11,
           IPV4_UNSUPPORT=12, UDP_HEADER_ERR=13, UDP_LEN_ERR=14, TCP_HEADER_ERR=15, TCP_LEN_ERR=16,
-          FLOW_TCP_NO_SYN_FIRST=17, WINDOW_PUNT=18, FLOW_NOMEM=19)
+          FLOW_TCP_NO_SYN_FIRST=17, WINDOW_PUNT=18, FLOW_NOMEM=19,
+          # StreamTcp's first-packet verdict (ppe_stream_tcp_set tracking on)
+          STREAM_RST_NO_SESSION=20, STREAM_FIN_NO_SESSION=21, STREAM_MIDSTREAM_ONESIDE_OFF=22,
+          STREAM_MIDSTREAM_OFF=23)
 ST_NAME = {v: k for k, v in ST.items()}
+# enum ppe_stream_counter (ppe_stream_counters_t.c[])
+STREAM_COUNTERS = ["syn_ack_count", "syn_count", "rst_count", "rst_but_no_session", "fin_but_no_session",
+                   "midstream_or_oneside_disable", "midstream_disable", "pkt_broken_ack"]
+PPE_EINVAL, PPE_ENOTSUP = -22, -95
 ACT_FW, ACT_DROP, ACT_PUNT = 0, 1, 2
 F_VLAN, F_L4, F_TCP, F_SYN, F_ACL, F_FRAG = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
 F_FLOW, F_TOCLIENT, F_NEWFLOW = 0x40, 0x80, 0x100
@@ -91,6 +98,21 @@ class Counters(C.Structure):
 
     def as_dict(self):
         return {name: int(self.c[i]) for i, name in enumerate(COUNTERS)}
+
+
+class StreamTcpCfg(C.Structure):  # ppe_stream_tcp_cfg_t
+    _fields_ = [("track", C.c_uint32), ("midstream", C.c_uint32), ("async_oneside", C.c_uint32),
+                ("reasm", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class StreamCounters(C.Structure):  # ppe_stream_counters_t
+    _fields_ = [("c", C.c_uint64 * 16)]
+
+    def as_dict(self):
+        return {name: int(self.c[i]) for i, name in enumerate(STREAM_COUNTERS)}
 
 
 class Tuning(C.Structure):
@@ -205,6 +227,8 @@ EXPORTS = [
     "ppe_steer_partition", "ppe_gather_rows", "ppe_scatter_rows",
     "ppe_defrag_create", "ppe_defrag_destroy", "ppe_defrag", "ppe_defrag_age", "ppe_defrag_info",
     "ppe_defrag_last_error",
+    "ppe_stream_tcp_set", "ppe_stream_tcp_get", "ppe_stream_counters_read", "ppe_stream_counters_clear",
+    "ppe_format_tcpstream_stat",
     # ppe_acl.h
     "ppe_rule_list_init", "ppe_rule_list_free", "Rule_add", "Rule_del_by_id", "Rule_del_all",
     "Rule_duplicate_check", "Rule_Load_Line", "ppe_rule_load_file", "DP_Acl_Rule_Init", "DP_Acl_Load_Rule",
@@ -215,7 +239,8 @@ EXPORTS = [
 ]
 EXPORTED_DATA = ["rule_list", "dp_acl_action_default", "gWstDepth", "gAvgDepth", "gChildCount", "gNumTreeNode",
                  "gNumLeafNode", "unsupport_proto_action", "syn_check", "plugin_modules", "g_acltree_1", "g_acltree_2",
-                 "g_acltree_running", "acltree_running_rwlock"]
+                 "g_acltree_running", "acltree_running_rwlock",
+                 "stream_tcp_track_enable", "stream_tcp_midstream", "stream_tcp_async_oneside"]
 
 _lib = None
 
@@ -301,6 +326,12 @@ def _open(p: Path, mode, strict: bool = True) -> C.CDLL:
         "ppe_defrag_age": ([vp, u64, u64, vp, u32, C.POINTER(u32), C.POINTER(u32)], C.c_int),
         "ppe_defrag_info": ([vp, C.POINTER(DefragInfo)], C.c_int),
         "ppe_defrag_last_error": ([vp], C.c_char_p),
+        "ppe_stream_tcp_set": ([vp, C.POINTER(StreamTcpCfg)], C.c_int),
+        "ppe_stream_tcp_get": ([vp, C.POINTER(StreamTcpCfg)], C.c_int),
+        "ppe_stream_counters_read": ([vp, C.POINTER(StreamCounters)], C.c_int),
+        "ppe_stream_counters_clear": ([vp], C.c_int),
+        "ppe_format_tcpstream_stat": ([C.POINTER(StreamCounters), C.POINTER(StreamTcpCfg), C.c_char_p, C.c_size_t],
+                                      C.c_int),
         "ppe_rule_list_init": ([], C.c_int),
         "ppe_rule_list_free": ([], None),
         "Rule_add": ([vp, C.POINTER(u32)], C.c_int),

@@ -8,7 +8,12 @@ dp_show_pkt_stat sums the per-core pktstat[] (dataplane/src/common/dp_cmd.c:844)
 """
 from __future__ import annotations
 
+import ctypes as C
+
 import numpy as np
+
+from . import abi
+from .engine import PPEError
 
 
 def shard_range(n: int, world: int, rank: int) -> tuple[int, int]:
@@ -102,6 +107,12 @@ class DeviceSteerOps:
                                                       out.data_ptr(), self._s()), "ppe_scatter_rows")
         return out
 
+    def stream_tracking(self) -> bool:
+        """ppe_stream_tcp_get: StreamTcp tracking is on for this engine (ppe_classify_flow then returns PPE_ENOTSUP)."""
+        cfg = abi.StreamTcpCfg()
+        self.eng._check(self.eng.lib.ppe_stream_tcp_get(self.eng.ctx, C.byref(cfg)), "ppe_stream_tcp_get")
+        return bool(cfg.track)
+
     def classify_flow(self, hdr, lens, cfg):
         t = self.torch
         n = lens.numel()
@@ -130,6 +141,11 @@ def steer_finish(ops, back, perm) -> dict:
 def steered_classify_flow(ops, dist, hdr, lens, cfg, world: int, rank: int) -> dict:
     """One batch of this rank through the flow tables of all ranks (collective: every rank calls it)."""
     import torch
+    # ppe_classify_flow refuses a tracked engine (PPE_ENOTSUP): surfaced here, before any collective, so that no rank
+    # is left waiting in an exchange for one that raised in its flow-table step
+    if getattr(ops, "stream_tracking", None) and ops.stream_tracking():
+        raise PPEError(f"ppe_classify_flow failed: {abi.PPE_ENOTSUP}: stream tracking is on (ppe_stream_tcp_set); "
+                       "the flow-table path does not support it")
     perm, counts, send_hdr, send_len = steer_prepare(ops, hdr, lens, cfg, world, rank)
     send_counts = counts.to(torch.int64)
     recv_counts = torch.empty_like(send_counts)

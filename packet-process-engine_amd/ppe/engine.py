@@ -203,6 +203,25 @@ class Engine:
     def clear_counters(self):
         self._check(self.lib.ppe_counters_clear(self.ctx), "ppe_counters_clear")
 
+    # ---- StreamTcp's first-packet verdict (ppe_stream_tcp_*, stream-tcp.c StreamTcpPacketStateNone) ----
+    def stream_tcp(self, track=1, midstream=0, async_oneside=0, reasm=None) -> dict:
+        """ppe_stream_tcp_set for later launches (a new context has tracking off); reasm (show text only) follows
+        track unless given.  Returns the setting read back."""
+        cfg = abi.StreamTcpCfg(int(track), int(midstream), int(async_oneside),
+                               int(track if reasm is None else reasm))
+        self._check(self.lib.ppe_stream_tcp_set(self.ctx, C.byref(cfg)), "ppe_stream_tcp_set")
+        got = abi.StreamTcpCfg()
+        self._check(self.lib.ppe_stream_tcp_get(self.ctx, C.byref(got)), "ppe_stream_tcp_get")
+        return got.as_dict()
+
+    def stream_counters(self) -> dict:
+        c = abi.StreamCounters()
+        self._check(self.lib.ppe_stream_counters_read(self.ctx, C.byref(c)), "ppe_stream_counters_read")
+        return c.as_dict()
+
+    def clear_stream_counters(self):
+        self._check(self.lib.ppe_stream_counters_clear(self.ctx), "ppe_stream_counters_clear")
+
     def timing(self, on: bool = True):
         self._check(self.lib.ppe_timing_enable(self.ctx, 1 if on else 0), "ppe_timing_enable")
 

@@ -416,3 +416,70 @@ def make_fragment_stream(n_dgrams: int, seed: int = SEED + 7, n_hosts: int = 64,
     for j, i in enumerate(order):
         arena[int(off[j]):int(off[j]) + int(lens[j])] = np.frombuffer(frames[i], np.uint8)
     return arena, off, lens
+
+
+# ---- TCP flag sweep (StreamTcp's first-packet verdict, ppe_stream_tcp_set) -------------------------------------------
+def make_tcp_flag_sweep(rules: np.ndarray, stride: int = 128, repeat: int = 1, seed: int = SEED + 11,
+                        ack: int = 0x01020304):
+    """Every first-packet case of StreamTcpPacketStateNone (stream-tcp.c:237-441) as 64-B frames: all 64 values of the
+    low six TCP flag bits x th_ack in {0, ack} x three layouts (plain; one VLAN tag; ihl = 6, the TCP header at a
+    data-dependent offset behind one option word) = 384 TCP packets over make_packets tuples (half of them drawn
+    inside `rules`), plus 64 UDP and 64 malformed packets; the 512 repeated `repeat` times (fresh tuples each time),
+    shuffled, then padded with plain SYN packets to 64 k + 37 packets (k >= 1 whole tiles beyond the sweep: 613
+    for repeat = 1).  Same dict as make_packets, plus th_flags (n,) int16 (-1: not a sweep TCP packet), th_ack (n,)
+    uint32 and layout (n,) int8 (0 plain, 1 VLAN, 2 ihl 6; -1 other)."""
+    rng = np.random.default_rng(seed)
+    hs, ls, ks, fs, acs, lys = [], [], [], [], [], []
+    for r in range(repeat):
+        base = make_packets(384, rules, seed=seed + 1 + 101 * r, kind="udp64", stride=stride, malformed_frac=0.0,
+                            tcp_frac=1.0)
+        hdr = np.zeros((384, stride), np.uint8)
+        flags = np.tile(np.arange(64, dtype=np.int16), 6)
+        acks = np.tile(np.repeat(np.array([0, ack], np.uint32), 64), 3)
+        layout = np.repeat(np.arange(3, dtype=np.int8), 128)
+        for i in range(384):
+            b, h = base["hdr"][i], hdr[i]
+            ip = b[14:34].copy()
+            ip[9] = 6
+            l3 = 18 if layout[i] == 1 else 14
+            ihl = 6 if layout[i] == 2 else 5
+            h[0:12] = b[0:12]
+            if layout[i] == 1:
+                h[12:18] = (0x81, 0x00, 0x00, 0x2A, 0x08, 0x00)
+            else:
+                h[12:14] = (0x08, 0x00)
+            ip[0] = 0x40 | ihl
+            _set16(ip, 2, 64 - l3)
+            h[l3:l3 + 20] = ip
+            h[l3 + 20:l3 + 4 * ihl] = 0x01  # NOP options
+            l4 = l3 + 4 * ihl
+            h[l4:l4 + 4] = b[34:38]  # ports
+            h[l4 + 4:l4 + 8] = (0, 0, 0, 1)
+            h[l4 + 8:l4 + 12] = [(int(acks[i]) >> s) & 0xFF for s in (24, 16, 8, 0)]
+            h[l4 + 12] = 0x50
+            h[l4 + 13] = flags[i]
+            _set16(h, l4 + 14, 1024)
+        udp = make_packets(64, rules, seed=seed + 2 + 101 * r, kind="udp64", stride=stride, malformed_frac=0.0,
+                           tcp_frac=0.0)
+        bad = make_packets(64, rules, seed=seed + 3 + 101 * r, kind="imix", stride=stride, malformed_frac=1.0)
+        hs += [hdr, udp["hdr"], bad["hdr"]]
+        ls += [np.full(384, 64, np.uint32), udp["len"], bad["len"]]
+        ks += [np.full(384, -1, np.int16), udp["kinds"], bad["kinds"]]
+        fs += [flags, np.full(128, -1, np.int16)]
+        acs += [acks, np.zeros(128, np.uint32)]
+        lys += [layout, np.full(128, -1, np.int8)]
+    hdr, lens, kinds = np.concatenate(hs), np.concatenate(ls), np.concatenate(ks)
+    flags, acks, layout = np.concatenate(fs), np.concatenate(acs), np.concatenate(lys)
+    perm = rng.permutation(len(lens))
+    hdr, lens, kinds, flags, acks, layout = hdr[perm], lens[perm], kinds[perm], flags[perm], acks[perm], layout[perm]
+    n = len(lens)
+    pad = 64 * ((n + 63) // 64 + 1) + 37 - n
+    first = int(np.flatnonzero((layout == 0) & (flags == 0x02) & (acks == 0))[0])  # a plain SYN
+    hdr = np.concatenate([hdr, np.repeat(hdr[first:first + 1], pad, axis=0)])
+    lens = np.concatenate([lens, np.full(pad, 64, np.uint32)])
+    kinds = np.concatenate([kinds, np.full(pad, -1, np.int16)])
+    flags = np.concatenate([flags, np.full(pad, 0x02, np.int16)])
+    acks = np.concatenate([acks, np.zeros(pad, np.uint32)])
+    layout = np.concatenate([layout, np.zeros(pad, np.int8)])
+    return dict(hdr=np.ascontiguousarray(hdr), len=lens, ts=None, kinds=kinds, th_flags=flags, th_ack=acks,
+                layout=layout)

@@ -36,6 +36,9 @@ def main():
     ap.add_argument("--binth", type=int, default=0)
     ap.add_argument("--variant", action="append", required=True, help="name=libpath[:key=val,...]")
     ap.add_argument("--check", action="store_true", help="compare every variant's outputs with the first")
+    ap.add_argument("--stream-tcp", action="store_true",
+                    help="StreamTcp tracking at the reference's defaults (ppe_stream_tcp_set(ctx, NULL)) on every "
+                         "variant whose library exports it; older builds run as they are")
     ap.add_argument("--reuse", action="store_true",
                     help="diagnostic: keep --nbufs buffers and reuse them within a launch (an on-die packet stream)")
     args = ap.parse_args()
@@ -95,6 +98,10 @@ def main():
         if "jump" in kvs:
             os.environ["PPE_JUMP_BITS"] = kvs.pop("jump")
         eng.commit(rules, default_action=1)
+        if args.stream_tcp and hasattr(eng.lib, "ppe_stream_tcp_set"):
+            eng.lib.ppe_stream_tcp_set.argtypes = [C.c_void_p, C.c_void_p]
+            assert eng.lib.ppe_stream_tcp_set(eng.ctx, None) == 0
+            name += "+stcp"
         os.environ.pop("PPE_JUMP_BITS", None)
         if kvs:
             eng.tuning(**{k: int(v) for k, v in kvs.items()})
