@@ -1,0 +1,313 @@
+/*
+ * launch_plan.cpp — how a classifier image is launched: a pure function of (image, tuning, stateless / flow-table).
+ *
+ * Host only: no HIP call, no context, no environment.  The engine computes a plan when an image is uploaded or the
+ * tuning changes and keeps it per image slot (ppe_engine.hip); tests/test_launch_plan.py checks it on the CPU against
+ * recorded plans.  The LDS sizes of the kernels (ppe_classify_fixed_lds, ppe_flow_lds_extra, ppe_flow_waves) stay in
+ * ppe_kernels.hip, whose macros an experimental build overrides (make variant).
+ */
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "ppe_hip.h"
+#include "ppe_image.h"
+#include "ppe_internal.h"
+
+namespace {
+
+// LDS left for the image per workgroup when the CU holds 2048 / block workgroups (32 waves; a flow-table launch:
+// the waves per CU its kernel is compiled for): 160 KiB shared, minus the per-wave walk keys and counter bins
+// (flow-table launches: and the owner-update buckets), and the 1-KB rounding of the staged image
+uint32_t image_budget(uint32_t block, int mode, bool flow = false) {
+    const uint32_t waves_cu = flow ? std::min(32u, std::max(block / 64u, 4u * ppe_flow_waves())) : 32u;
+    const uint32_t per_wg = (160u * 1024u) / std::max(1u, waves_cu / (block / 64u));
+    const uint32_t fixed = ppe_classify_fixed_lds((int)block, PF_HOIST, mode) + 1024u + (flow ? ppe_flow_lds_extra() : 0u);
+    return per_wg > fixed ? per_wg - fixed : 0u;
+}
+
+// Image placement, tile fetch, workgroup size and LDS offsets, into p (zeroed but for the ~0u "from global memory"
+// offsets).  lds_nodes: the binary nodes a single-tile walk finds in its staged prefix.
+// single: the plan for the single-tile node-walk kernel only (the flow-table classify kernel is built for it: its
+// key slots and node prefix), never the multi-tile or cut-list plans
+void stage_plan(const ppe_tuning_t &tune, const uint32_t *img, uint32_t n_words, bool single, ppe_plan &p,
+                uint32_t &lds_nodes) {
+    const uint32_t pf = tune.pipeline == 1 ? PF_NONE : PF_HOIST;
+    // the single-tile walk reads the binary nodes only: what it stages "whole" is the image before the block section
+    const uint32_t all_words = img[PPE_IMG_W_OFFCUT] ? img[PPE_IMG_W_OFFCUT] : n_words;  // tree part
+    const uint32_t off_bsec = img[PPE_IMG_W_OFFBSEC], off_blocks = img[PPE_IMG_W_OFFBLOCKS];
+    const uint32_t n_blocks = img[PPE_IMG_W_NBLOCKS];
+    const uint32_t words = off_bsec, bytes = words * 4u;
+    p.mode = IMG_GLOBAL;
+    p.pipe = pf;
+    p.block = tune.block ? tune.block : 1024u;
+    // the multi-tile walk reads the 2-level blocks: whole image in LDS, else the block jump table and the first
+    // block levels (breadth-first), else global
+    const uint32_t off_crec = img[PPE_IMG_W_OFFCREC], off_idtab = img[PPE_IMG_W_OFFIDTAB];
+    constexpr uint32_t bbytes = 32u;
+    auto mt_plan = [&](uint32_t budget) {
+        const uint32_t bjt = 4u * (off_blocks - off_bsec);
+        if (off_crec && (all_words - off_bsec) * 4u <= budget) {
+            // compact image (v6): the block walk needs only the block section and the compact records after it, so
+            // the whole walk is LDS-resident when they fit (C2 / C4: 4,096 rules, ~140 KB)
+            p.mode = IMG_LDS;
+            p.stage_src = off_bsec;
+            p.lds_words = p.stage_words = all_words - off_bsec;
+            p.lds_blocks = n_blocks;
+            p.bsec_lds = 0;
+            p.blk_lds = 4u * (off_blocks - off_bsec);
+            p.crec_lds = 4u * (off_crec - off_bsec);
+            if (off_idtab) p.idtab_lds = 4u * (off_idtab - off_bsec);
+        } else if (!off_crec && all_words * 4u <= budget) {
+            p.mode = IMG_LDS;
+            p.lds_words = p.stage_words = all_words;
+            p.lds_blocks = n_blocks;
+            p.bsec_lds = 4u * off_bsec;
+            p.blk_lds = 4u * off_blocks;
+        } else if (budget >= bjt + bbytes * 64u) {
+            p.mode = IMG_SPLIT;
+            p.lds_blocks = std::min(n_blocks, (budget - bjt) / bbytes);
+            p.stage_src = off_bsec;
+            p.stage_words = (off_blocks - off_bsec) + (bbytes / 4u) * p.lds_blocks;
+            p.bsec_lds = 0;
+            p.blk_lds = bjt;
+        }
+    };
+    // the cut lists (image v8): the bucket groups in LDS (the smallest workgroup whose share at 32 waves per CU holds
+    // them; the entries too when they fit beside them), the entries read from L2 otherwise; one tile per wave at 8
+    // waves per SIMD.  lds_image = 0: both from global memory.
+    const uint32_t off_cut = img[PPE_IMG_W_OFFCUT];
+    auto cut_plan = [&]() {
+        const uint32_t *h = img + off_cut;
+        const uint32_t grp_bytes = 4u * (h[5] - h[4]);  // slices, bases and fingerprints (the L2-entry plan's LDS)
+        const uint32_t all_words = h[5] - h[4] + 32u * h[11] +  // ... to the end of the entry lines (and the ids)
+                                   (h[0] & PPE_CUT_LINES ? 0u : h[0] & PPE_CUT_IDS16 ? (h[2] + 1u) / 2u : h[2]);
+        p.pipe = PF_CUT;
+        p.mode = IMG_GLOBAL;
+        p.block = tune.block ? tune.block : 1024u;
+        p.cut_ent_lds = ~0u;  // (entry lines from global memory unless staged below)
+        if (!tune.lds_image) return;
+        auto budget = [&](uint32_t b) {  // (no key slots: the keys stay in registers)
+            const uint32_t per_wg = (160u * 1024u) / std::max(1u, 32u / (b / 64u));
+            const uint32_t fixed = ppe_classify_fixed_lds((int)b, PF_CUT, IMG_LDS) + 1024u;
+            return per_wg > fixed ? per_wg - fixed : 0u;
+        };
+        if (!tune.block)
+            for (uint32_t b : {256u, 512u, 1024u})
+                if (4u * all_words <= budget(b) || (b == 1024u && grp_bytes <= budget(b))) {
+                    p.block = b;
+                    break;
+                }
+        const uint32_t bud = budget(p.block);
+        if (grp_bytes > bud) return;  // (groups larger than the share: global)
+        p.stage_src = h[4];
+        p.cut_gbase_lds = 4u * (h[8] - h[4]);
+        p.cut_fp_lds = 4u * (h[9] - h[4]);
+        // everything in LDS (IMG_LDS: the dense layout only, the kernel's entry addressing assumes it)
+        if (4u * all_words <= bud && !(h[0] & PPE_CUT_LINES)) {
+            p.mode = IMG_LDS;
+            p.stage_words = all_words;
+            p.cut_ent_lds = 4u * (h[5] - h[4]);
+        } else {  // slices, bases and fingerprints in LDS, the entry lines from L2 (IMG_SPLIT)
+            p.mode = IMG_SPLIT;
+            p.stage_words = h[5] - h[4];
+        }
+        p.lds_words = p.stage_words;
+    };
+    if (!single && off_cut && tune.pipeline == 5) {
+        cut_plan();
+        return;
+    }
+    if (!tune.lds_image) {
+        if (!tune.block) p.block = 256;
+        if (!single && (tune.pipeline == 3 || (tune.pipeline == 0 && !tune.block))) {  // PF_MULTI, global image
+            p.pipe = PF_MULTI;
+            p.block = 1024u;
+        }
+        return;
+    }
+    // the whole image in LDS: the smallest workgroup (most copies per CU) whose share holds it (a node walk reads
+    // the part before the block section)
+    const uint32_t lds_bytes = bytes;
+    if (!tune.block) {
+        for (uint32_t b : {256u, 512u, 1024u}) {
+            if (lds_bytes <= image_budget(b, IMG_LDS, single)) {
+                p.block = b;
+                break;
+            }
+        }
+    }
+    uint32_t budget = image_budget(p.block, IMG_LDS, single);
+    const bool fits = lds_bytes <= budget;
+    // images that do not fit whole: the cut lists when the image has them (C2 / C3 / C4), else PF_MULTI
+    // (1024-thread workgroups, one per CU, with the CU's whole LDS for the image prefix: C2 / C3 / C4 step 27.2 /
+    // 52.1 / 27.3 -> 23.6 / 42.8 / 22.7 us against the single-tile node walk)
+    if (!single && off_cut && tune.pipeline == 0 && !fits && !tune.block) {
+        cut_plan();
+        return;
+    }
+    if (!single && (tune.pipeline == 3 || (tune.pipeline == 0 && !fits && !tune.block))) {
+        p.pipe = PF_MULTI;
+        p.block = 1024u;
+        const uint32_t fixed = ppe_classify_fixed_lds((int)p.block, PF_MULTI, IMG_SPLIT) + 1024u;  // no key slots
+        mt_plan(160u * 1024u - fixed);  // one workgroup per CU: all of its LDS
+        return;
+    }
+    const uint32_t off_resid = img[PPE_IMG_W_OFFRESID], off_rules = img[PPE_IMG_W_OFFRULES];
+    const uint32_t n_nodes = img[PPE_IMG_W_NNODES], off_nodes = img[PPE_IMG_W_OFFNODES];
+    if (fits) {
+        p.mode = IMG_LDS;
+        p.lds_words = p.stage_words = words;
+        return;
+    }
+    budget = image_budget(p.block, IMG_SPLIT, single);  // node walks of a partly staged image keep their key slots
+    if (off_resid * 4u <= budget) {  // nodes, leaf lists and rule records; residual records from global
+        p.mode = IMG_SPLIT;
+        p.lds_words = off_resid;
+        lds_nodes = n_nodes;
+    } else if (off_rules * 4u <= budget) {  // every node and leaf list; rule records from global (L2)
+        p.mode = IMG_SPLIT;
+        p.lds_words = off_rules;
+        lds_nodes = n_nodes;
+    } else if (budget >= 4u * (off_nodes + PPE_NODE_WORDS * 64u)) {  // header, jump table, top of the BFS forest
+        p.mode = IMG_SPLIT;
+        lds_nodes = std::min(n_nodes, (budget / 4u - off_nodes) / PPE_NODE_WORDS);
+        p.lds_words = off_nodes + PPE_NODE_WORDS * lds_nodes;
+    }
+    p.stage_words = p.lds_words;  // single-tile walks stage a prefix from word 0
+}
+
+// Walk levels (node reads) whose nodes all lie in the first lds_nodes nodes of the image
+uint32_t levels_within(const uint32_t *words, uint32_t lds_nodes) {
+    // BFS node order: the nodes of depth <= d are exactly [0, level_end[d])
+    std::vector<uint32_t> le;
+    const uint32_t nn = words[PPE_IMG_W_NNODES], on = words[PPE_IMG_W_OFFNODES];
+    std::vector<uint8_t> depth(nn, 0);  // every root of the forest (jump root: several) has depth 0
+    for (uint32_t k = 0; k < nn; ++k) {
+        const uint32_t *nd = words + on + PPE_NODE_WORDS * k;
+        if (nd[0] != PPE_LEAF_THR) {  // children: byte offsets from the image start
+            depth[(nd[1] / 4u - on) / PPE_NODE_WORDS] = (uint8_t)(depth[k] + 1u);
+            depth[(nd[2] / 4u - on) / PPE_NODE_WORDS] = (uint8_t)(depth[k] + 1u);
+        }
+        if (le.size() <= depth[k]) le.resize(depth[k] + 1u, 0u);
+        le[depth[k]] = k + 1u;
+    }
+    uint32_t L = 0;
+    while (L < le.size() && le[L] <= lds_nodes) ++L;
+    return L;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ppe_plan_image(const uint32_t *words, uint32_t n_words, const ppe_tuning_t *t, int flow, struct ppe_plan *out) {
+    if (!words || !t || !out || n_words < PPE_IMG_HDR_WORDS || words[0] != PPE_IMG_MAGIC ||
+        words[1] != PPE_IMG_VERSION)
+        return PPE_EINVAL;
+    if (t->block != 0 && t->block != 256 && t->block != 512 && t->block != 1024) return PPE_EINVAL;
+    ppe_plan p;
+    std::memset(&p, 0, sizeof p);
+    p.crec_lds = p.idtab_lds = ~0u;  // compact records / index table: read from global memory
+    uint32_t lds_nodes = 0;
+    stage_plan(*t, words, n_words, flow != 0, p, lds_nodes);
+    // (what ppe_launch_classify allocates: the kernel's fixed LDS and the staged words rounded to 1 KB)
+    p.lds_bytes = ppe_classify_fixed_lds((int)p.block, (int)p.pipe, (int)p.mode) + (flow ? ppe_flow_lds_extra() : 0u) +
+                  (p.mode ? ((p.stage_words * 4u + 1023u) & ~1023u) : 0u);
+    p.img_words = n_words;
+    p.default_action = words[PPE_IMG_W_DEFACT];
+    p.off_bsec = words[PPE_IMG_W_OFFBSEC];
+    p.off_blocks = words[PPE_IMG_W_OFFBLOCKS];
+    p.max_bdepth = words[PPE_IMG_W_MAXBDEPTH];
+    p.off_crec = words[PPE_IMG_W_OFFCREC];
+    p.off_idtab = words[PPE_IMG_W_OFFIDTAB];
+    if (p.pipe == PF_CUT) {  // (image v8 cut lists: header at PPE_IMG_W_OFFCUT)
+        const uint32_t *h = words + words[PPE_IMG_W_OFFCUT];
+        p.cut = h[0];
+        p.cut_slc = h[4];
+        p.cut_ent = h[5];
+        p.cut_epl = h[7];
+        p.cut_div = h[10];
+        p.cut_idrel = (h[0] & PPE_CUT_LINES) ? 0u : 4u * (h[12] - h[5]);
+        p.cut_gbase = h[8];
+        p.cut_fp = h[9];
+    }
+    p.max_depth = words[PPE_IMG_W_MAXDEPTH];
+    p.max_leaf = words[PPE_IMG_W_MAXLEAF];
+    p.root_ks = words[PPE_IMG_W_ROOTKS];
+    p.jump = words[PPE_IMG_W_JUMP];
+    p.off_nodes = words[PPE_IMG_W_OFFNODES];
+    if (p.mode == IMG_LDS) {
+        p.lds_iters = p.max_depth + 1u;
+    } else if (p.mode == IMG_SPLIT) {  // node reads 0..L-1 only visit depths < L: all inside the staged prefix
+        p.lds_iters = std::min(levels_within(words, lds_nodes), p.max_depth + 1u);
+    }
+    p.off_leaf = words[PPE_IMG_W_OFFLEAF];
+    p.off_rules = words[PPE_IMG_W_OFFRULES];
+    p.off_resid = words[PPE_IMG_W_OFFRESID];
+    *out = p;
+    return PPE_OK;
+}
+
+void ppe_plan_apply(struct ppe_kargs *a, const struct ppe_plan *p) {
+    a->img_words = p->img_words;
+    a->default_action = p->default_action;
+    a->lds_words = p->lds_words;
+    a->stage_src = p->stage_src;
+    a->stage_words = p->stage_words;
+    a->lds_blocks = p->lds_blocks;
+    a->bsec_lds = p->bsec_lds;
+    a->blk_lds = p->blk_lds;
+    a->off_bsec = p->off_bsec;
+    a->off_blocks = p->off_blocks;
+    a->max_bdepth = p->max_bdepth;
+    a->off_crec = p->off_crec;
+    a->off_idtab = p->off_idtab;
+    a->crec_lds = p->crec_lds;
+    a->idtab_lds = p->idtab_lds;
+    a->cut = p->cut;
+    a->cut_slc = p->cut_slc;
+    a->cut_gbase = p->cut_gbase;
+    a->cut_fp = p->cut_fp;
+    a->cut_ent = p->cut_ent;
+    a->cut_epl = p->cut_epl;
+    a->cut_div = p->cut_div;
+    a->cut_idrel = p->cut_idrel;
+    a->cut_gbase_lds = p->cut_gbase_lds;
+    a->cut_fp_lds = p->cut_fp_lds;
+    a->cut_ent_lds = p->cut_ent_lds;
+    a->lds_iters = p->lds_iters;
+    a->max_depth = p->max_depth;
+    a->max_leaf = p->max_leaf;
+    a->root_ks = p->root_ks;
+    a->jump = p->jump;
+    a->off_nodes = p->off_nodes;
+    a->off_leaf = p->off_leaf;
+    a->off_rules = p->off_rules;
+    a->off_resid = p->off_resid;
+}
+
+// Batch groups: the kernel splits its waves into min(batches, max_groups) groups, group g taking batches g, g + G,
+// ...; when G does not divide the batch count the last round leaves groups idle (20 batches at G = 8: the last
+// 4 run on half the grid; C3 / C4 ring step +12 %, profiles/r3_ab_runs.md r4l).  Take the power-of-two G up to the
+// cap (or the batch count itself when smaller) with the least work-slot time, ceil(batches / G) x G batch slots
+// weighted by the per-batch cost of G groups (1 group 1.10, 2 groups 1.02, more 1.00: C1 per-batch 20.2 / 18.7 /
+// 18.3 us at 1 / 2 / >= 4 groups); ties go to the larger G.  20 batches -> 4 groups, 32 -> 8, 33 -> 2.
+uint32_t ppe_pick_groups(uint32_t nb, uint32_t max_groups) {
+    const uint32_t gmax = std::max(1u, std::min(max_groups, nb));
+    auto cost = [&](uint32_t g) {
+        return (double)((nb + g - 1u) / g * g) * (g == 1u ? 1.10 : g == 2u ? 1.02 : 1.0);
+    };
+    uint32_t best = gmax;
+    double cbest = cost(gmax);
+    for (uint32_t g = 1u << (31 - __builtin_clz(gmax)); g >= 1u; g >>= 1) {
+        if (g == gmax) continue;
+        if (cost(g) < cbest - 1e-9) {
+            best = g;
+            cbest = cost(g);
+        }
+    }
+    return best;
+}
+
+}  // extern "C"

@@ -30,11 +30,6 @@ constexpr int kHostStreams = 3;
 // ppe_classify_batches: two streams, so a batch's launch ramp-up overlaps the previous batch's tail (C1: 20.6 ->
 // 16.5 us per batch; three streams measured 17.0)
 constexpr int kPipeStreams = 2;
-// tile fetch / walk of the classify kernel (PF_* in ppe_kernels.hip): 0 one tile per wave, its window at the loop
-// top; 1 the first tile's loads issued before the image staging (C1 21.7 us vs 22.2); 3 the multi-tile block walk;
-// 5 the cut lists (image v8).  Register double-buffering (next tile's window, or only its first 16 B, requested
-// before the current tile is processed) and an LDS-DMA next-tile pipeline were measured slower.
-constexpr int kPfNone = 0, kPfHoist = 1, kPfMulti = 3, kPfCut = 5;
 constexpr uint32_t kMaxBlocksPerCU = 32;  // > resident: the grid then runs in rounds (non-persistent)
 // ppe_classify_batches: batches per launch.  0 = every batch of the call in one persistent launch (descriptor ring in
 // device memory): the launch ramp and tail are paid once per call instead of once per batch
@@ -123,7 +118,10 @@ struct ppe_ctx {
     uint32_t *d_img[2] = {nullptr, nullptr};
     size_t img_cap[2] = {0, 0};
     std::vector<uint32_t> h_img[2];
-    std::vector<uint32_t> level_end[2];  // per image: number of tree nodes at depth <= d (BFS order)
+    // per image: its launch plan under `tune`, stateless / flow-table (csrc/launch_plan.cpp), and that plan's resident
+    // workgroups per CU (0: not asked yet, blocks_per_cu)
+    ppe_plan plan[2][2] = {};
+    uint32_t plan_bpc[2][2] = {};
     ppe_acl_stats_t stats[2];
     hipEvent_t img_done[2] = {nullptr, nullptr};
     std::vector<Reader> img_readers[2];  // per slot: launch streams, their last launch with it
@@ -164,7 +162,6 @@ struct ppe_ctx {
     int ring_next = 0;
     std::vector<ppe_bdesc> ring_tmp;   // descriptors of the launch being built
     ppe_tuning_t tune;
-    std::vector<std::pair<uint64_t, uint32_t>> occ_cache;  // resident workgroups per CU by kernel variant
     // batch groups of waves a launch may split into (PPE_GROUPS): more groups = more tiles per wave between batch
     // setups, but more batches streamed at once (DRAM locality); C1, 20-32 batches per launch, per batch: 1 / 2 / 4
     // / 8 / 32 groups 20.2 / 18.7 / 18.3 / 18.3 / 19.1 us (one run, tools/ab_bench.py)
@@ -215,198 +212,32 @@ ppe_tuning_t default_tuning() {
     return t;
 }
 
-// How the classify kernel holds the classifier image (see IMG_* in ppe_kernels.hip) and how it fetches tiles.
-struct StagePlan {
-    int mode;            // 0 global, 1 whole image in LDS, 2 prefix in LDS
-    int pipe;            // tile fetch (kPf*)
-    uint32_t block;
-    uint32_t lds_words, lds_nodes;  // image words staged from word 0 (single-tile walks: binary nodes)
-    uint32_t stage_src, stage_words;  // what the kernel copies into LDS: image words [stage_src, + stage_words)
-    uint32_t lds_blocks;              // multi-tile walks: blocks [0, lds_blocks) in LDS
-    uint32_t bsec_lds, blk_lds;       // LDS byte offsets (from the image base in LDS) of the block section / block 0
-    uint32_t crec_lds = ~0u, idtab_lds = ~0u;  // compact records / index table in LDS (byte offsets), ~0u = global
-    uint32_t cut_gbase_lds = 0, cut_fp_lds = 0;    // cut lists: LDS byte offsets of the group bases / fingerprints
-    uint32_t cut_ent_lds = ~0u;                    // cut lists: entry lines in LDS (byte offset), ~0u = global
-};
-
-// LDS left for the image per workgroup when the CU holds 2048 / block workgroups (32 waves; a flow-table launch:
-// the waves per CU its kernel is compiled for): 160 KiB shared, minus the per-wave walk keys and counter bins
-// (flow-table launches: and the owner-update buckets), and the 1-KB rounding of the staged image
-uint32_t image_budget(uint32_t block, int mode, bool flow = false) {
-    const uint32_t waves_cu = flow ? std::min(32u, std::max(block / 64u, 4u * ppe_flow_waves())) : 32u;
-    const uint32_t per_wg = (160u * 1024u) / std::max(1u, waves_cu / (block / 64u));
-    const uint32_t fixed = ppe_classify_fixed_lds((int)block, kPfHoist, mode) + 1024u + (flow ? ppe_flow_lds_extra() : 0u);
-    return per_wg > fixed ? per_wg - fixed : 0u;
-}
-
-// single: the plan for the single-tile node-walk kernel only (the flow-table classify kernel is built for it: its
-// key slots and node prefix), never the multi-tile or cut-list plans
-StagePlan stage_plan(const ppe_ctx *c, const std::vector<uint32_t> &img, bool single = false) {
-    const int pf = c->tune.pipeline == 1 ? kPfNone : kPfHoist;
-    // the single-tile walk reads the binary nodes only: what it stages "whole" is the image before the block section
-    const uint32_t all_words = img[PPE_IMG_W_OFFCUT] ? img[PPE_IMG_W_OFFCUT] : (uint32_t)img.size();  // tree part
-    const uint32_t off_bsec = img[PPE_IMG_W_OFFBSEC], off_blocks = img[PPE_IMG_W_OFFBLOCKS];
-    const uint32_t n_blocks = img[PPE_IMG_W_NBLOCKS];
-    const uint32_t words = off_bsec, bytes = words * 4u;
-    StagePlan p = {0, pf, c->tune.block ? c->tune.block : 1024u, 0, 0, 0, 0, 0, 0, 0};
-    // the multi-tile walk reads the 2-level blocks: whole image in LDS, else the block jump table and the first
-    // block levels (breadth-first), else global
-    const uint32_t off_crec = img[PPE_IMG_W_OFFCREC], off_idtab = img[PPE_IMG_W_OFFIDTAB];
-    constexpr uint32_t bbytes = 32u;
-    auto mt_plan = [&](uint32_t budget) {
-        const uint32_t bjt = 4u * (off_blocks - off_bsec);
-        if (off_crec && (all_words - off_bsec) * 4u <= budget) {
-            // compact image (v6): the block walk needs only the block section and the compact records after it, so
-            // the whole walk is LDS-resident when they fit (C2 / C4: 4,096 rules, ~140 KB)
-            p.mode = 1;
-            p.stage_src = off_bsec;
-            p.lds_words = p.stage_words = all_words - off_bsec;
-            p.lds_blocks = n_blocks;
-            p.bsec_lds = 0;
-            p.blk_lds = 4u * (off_blocks - off_bsec);
-            p.crec_lds = 4u * (off_crec - off_bsec);
-            if (off_idtab) p.idtab_lds = 4u * (off_idtab - off_bsec);
-        } else if (!off_crec && all_words * 4u <= budget) {
-            p.mode = 1;
-            p.lds_words = p.stage_words = all_words;
-            p.lds_blocks = n_blocks;
-            p.bsec_lds = 4u * off_bsec;
-            p.blk_lds = 4u * off_blocks;
-        } else if (budget >= bjt + bbytes * 64u) {
-            p.mode = 2;
-            p.lds_blocks = std::min(n_blocks, (budget - bjt) / bbytes);
-            p.stage_src = off_bsec;
-            p.stage_words = (off_blocks - off_bsec) + (bbytes / 4u) * p.lds_blocks;
-            p.bsec_lds = 0;
-            p.blk_lds = bjt;
-        }
-    };
-    // the cut lists (image v8): the bucket groups in LDS (the smallest workgroup whose share at 32 waves per CU holds
-    // them; the entries too when they fit beside them), the entries read from L2 otherwise; one tile per wave at 8
-    // waves per SIMD.  lds_image = 0: both from global memory.
-    const uint32_t off_cut = img[PPE_IMG_W_OFFCUT];
-    auto cut_plan = [&]() {
-        const uint32_t *h = img.data() + off_cut;
-        const uint32_t grp_bytes = 4u * (h[5] - h[4]);  // slices, bases and fingerprints (the L2-entry plan's LDS)
-        const uint32_t all_words = h[5] - h[4] + 32u * h[11] +  // ... to the end of the entry lines (and the ids)
-                                   (h[0] & PPE_CUT_LINES ? 0u : h[0] & PPE_CUT_IDS16 ? (h[2] + 1u) / 2u : h[2]);
-        p.pipe = kPfCut;
-        p.mode = 0;
-        p.block = c->tune.block ? c->tune.block : 1024u;
-        if (!c->tune.lds_image) return;
-        auto budget = [&](uint32_t b) {  // (no key slots: the keys stay in registers)
-            const uint32_t per_wg = (160u * 1024u) / std::max(1u, 32u / (b / 64u));
-            const uint32_t fixed = ppe_classify_fixed_lds((int)b, kPfCut, 1) + 1024u;
-            return per_wg > fixed ? per_wg - fixed : 0u;
-        };
-        if (!c->tune.block)
-            for (uint32_t b : {256u, 512u, 1024u})
-                if (4u * all_words <= budget(b) || (b == 1024u && grp_bytes <= budget(b))) {
-                    p.block = b;
-                    break;
-                }
-        const uint32_t bud = budget(p.block);
-        if (grp_bytes > bud) return;  // (groups larger than the share: global)
-        p.stage_src = h[4];
-        p.cut_gbase_lds = 4u * (h[8] - h[4]);
-        p.cut_fp_lds = 4u * (h[9] - h[4]);
-        // everything in LDS (IMG_LDS: the dense layout only, the kernel's entry addressing assumes it)
-        if (4u * all_words <= bud && !(h[0] & PPE_CUT_LINES) && env_int("PPE_CUT_ENT_LDS", 1)) {
-            p.mode = 1;
-            p.stage_words = all_words;
-            p.cut_ent_lds = 4u * (h[5] - h[4]);
-        } else {  // slices, bases and fingerprints in LDS, the entry lines from L2 (IMG_SPLIT)
-            p.mode = 2;
-            p.stage_words = h[5] - h[4];
-        }
-        p.lds_words = p.stage_words;
-    };
-    if (!single && off_cut && c->tune.pipeline == 5) {
-        cut_plan();
-        return p;
-    }
-    if (!c->tune.lds_image) {
-        if (!c->tune.block) p.block = 256;
-        if (!single && (c->tune.pipeline == 3 || (c->tune.pipeline == 0 && !c->tune.block))) {  // PF_MULTI, global image
-            p.pipe = kPfMulti;
-            p.block = 1024u;
-        }
-        return p;
-    }
-    // the whole image in LDS: the smallest workgroup (most copies per CU) whose share holds it (a node walk reads
-    // the part before the block section)
-    const uint32_t lds_bytes = bytes;
-    if (!c->tune.block) {
-        for (uint32_t b : {256u, 512u, 1024u}) {
-            if (lds_bytes <= image_budget(b, 1, single)) {
-                p.block = b;
-                break;
-            }
-        }
-    }
-    uint32_t budget = image_budget(p.block, 1, single);
-    const bool fits = lds_bytes <= budget;
-    // images that do not fit whole: the cut lists when the image has them (C2 / C3 / C4), else PF_MULTI
-    // (1024-thread workgroups, one per CU, with the CU's whole LDS for the image prefix: C2 / C3 / C4 step 27.2 /
-    // 52.1 / 27.3 -> 23.6 / 42.8 / 22.7 us against the single-tile node walk)
-    if (!single && off_cut && c->tune.pipeline == 0 && !fits && !c->tune.block && env_int("PPE_CUT_PLAN", 1)) {
-        cut_plan();
-        return p;
-    }
-    if (!single && (c->tune.pipeline == 3 || (c->tune.pipeline == 0 && !fits && !c->tune.block))) {
-        p.pipe = kPfMulti;
-        // tuning knobs (A/B only): workgroup size and the LDS bytes each workgroup may take (default: all of it, one
-        // workgroup per CU); less LDS lets more workgroups share a CU
-        const int mb = env_int("PPE_MT_BLOCK", 1024);
-        p.block = (mb == 256 || mb == 512) ? (uint32_t)mb : 1024u;
-        const uint32_t fixed = ppe_classify_fixed_lds((int)p.block, kPfMulti, 2) + 1024u;  // no key slots
-        const uint32_t cap = (uint32_t)std::min(160 * 1024, std::max(8 * 1024, env_int("PPE_MT_LDS", 160 * 1024)));
-        budget = cap > fixed ? cap - fixed : 0u;
-        mt_plan(budget);
-        return p;
-    }
-    const uint32_t off_resid = img[PPE_IMG_W_OFFRESID], off_rules = img[PPE_IMG_W_OFFRULES];
-    const uint32_t n_nodes = img[PPE_IMG_W_NNODES], off_nodes = img[PPE_IMG_W_OFFNODES];
-    if (fits) {
-        p.mode = 1;
-        p.lds_words = p.stage_words = words;
-        return p;
-    }
-    budget = image_budget(p.block, 2, single);  // node walks of a partly staged image keep their key slots
-    if (off_resid * 4u <= budget) {  // nodes, leaf lists and rule records; residual records from global
-        p.mode = 2;
-        p.lds_words = off_resid;
-        p.lds_nodes = n_nodes;
-    } else if (off_rules * 4u <= budget) {  // every node and leaf list; rule records from global (L2)
-        p.mode = 2;
-        p.lds_words = off_rules;
-        p.lds_nodes = n_nodes;
-    } else if (budget >= 4u * (off_nodes + PPE_NODE_WORDS * 64u)) {  // header, jump table, top of the BFS forest
-        p.mode = 2;
-        p.lds_nodes = std::min(n_nodes, (budget / 4u - off_nodes) / PPE_NODE_WORDS);
-        p.lds_words = off_nodes + PPE_NODE_WORDS * p.lds_nodes;
-    }
-    p.stage_words = p.lds_words;  // single-tile walks stage a prefix from word 0
-    return p;
-}
-
-// Resident workgroups per CU: the occupancy API's answer (register and LDS limits) unless the tuning fixes it.
-// The persistent grid is CUs × this, so no workgroup waits for a second round.
-uint32_t blocks_per_cu(ppe_ctx *c, const StagePlan &p, bool flow = false) {
+// Resident workgroups per CU of slot r's plan (fl: its flow-table plan): the occupancy API's answer (register and LDS
+// limits) unless the tuning fixes it.  The persistent grid is CUs × this, so no workgroup waits for a second round.
+// The occupancy query costs microseconds of host time: asked on the plan's first launch and kept with the plan (a
+// flow-table launch: the flow variant's own occupancy, so its grid is resident in one round and each workgroup's
+// owner-update buckets hold as many entries as it can)
+uint32_t blocks_per_cu(ppe_ctx *c, int r, bool fl = false) {
+    const ppe_plan &p = c->plan[r][fl];
     const uint32_t cap = kMaxBlocksPerCU * 256u / p.block;
     if (c->tune.blocks_per_cu) return std::max(1u, std::min(c->tune.blocks_per_cu, cap));  // may exceed residency
-    // the occupancy query costs microseconds of host time per call: cached per kernel variant and LDS size (a
-    // flow-table launch: the flow variant's own occupancy, so its grid is resident in one round and each workgroup's
-    // owner-update buckets hold as many entries as it can)
-    const uint64_t key = (uint64_t)p.stage_words | ((uint64_t)p.mode << 32) | ((uint64_t)p.pipe << 40) |
-                         ((uint64_t)p.block << 48) | ((uint64_t)(flow ? 1u : 0u) << 63);
-    for (const auto &e : c->occ_cache)
-        if (e.first == key) return e.second;
-    const int occ = flow ? ppe_classify_occupancy_flow(p.stage_words, p.mode, (int)p.block)
-                         : ppe_classify_occupancy(p.stage_words, p.mode, p.pipe, (int)p.block);
-    const uint32_t r = occ > 0 ? std::min<uint32_t>((uint32_t)occ, cap) : 1u;
-    c->occ_cache.emplace_back(key, r);
-    return r;
+    uint32_t &bpc = c->plan_bpc[r][fl];
+    if (!bpc) {
+        const int occ = fl ? ppe_classify_occupancy_flow(p.stage_words, (int)p.mode, (int)p.block)
+                           : ppe_classify_occupancy(p.stage_words, (int)p.mode, (int)p.pipe, (int)p.block);
+        bpc = occ > 0 ? std::min<uint32_t>((uint32_t)occ, cap) : 1u;
+    }
+    return bpc;
+}
+
+// The plans of slot r's image under the context's tuning (after an upload or a tuning change)
+int plan_slot(ppe_ctx *c, int r) {
+    for (int fl = 0; fl < 2; ++fl) {
+        if (ppe_plan_image(c->h_img[r].data(), (uint32_t)c->h_img[r].size(), &c->tune, fl, &c->plan[r][fl]) != PPE_OK)
+            return fail(c, PPE_EINVAL, "no launch plan for the classifier image in slot %d", r);
+        c->plan_bpc[r][fl] = 0;
+    }
+    return PPE_OK;
 }
 
 // A launch on stream s reads slot r of an image or descriptor ring: an event (one per slot and stream) is recorded
@@ -526,50 +357,24 @@ int upload_image(ppe_ctx *c, int slot, uint32_t *words, uint32_t n_words, const 
     HIPCHK(c, hipMemcpyAsync(c->d_img[slot], words, bytes, hipMemcpyHostToDevice, c->aux));
     HIPCHK(c, hipStreamSynchronize(c->aux));
     c->h_img[slot].assign(words, words + n_words);
-    // BFS node order: the nodes of depth <= d are exactly [0, level_end[d])
-    {
-        std::vector<uint32_t> &le = c->level_end[slot];
-        le.clear();
-        const uint32_t nn = words[PPE_IMG_W_NNODES], on = words[PPE_IMG_W_OFFNODES];
-        std::vector<uint8_t> depth(nn, 0);  // every root of the forest (jump root: several) has depth 0
-        for (uint32_t k = 0; k < nn; ++k) {
-            const uint32_t *nd = words + on + PPE_NODE_WORDS * k;
-            if (nd[0] != PPE_LEAF_THR) {  // children: byte offsets from the image start
-                depth[(nd[1] / 4u - on) / PPE_NODE_WORDS] = (uint8_t)(depth[k] + 1u);
-                depth[(nd[2] / 4u - on) / PPE_NODE_WORDS] = (uint8_t)(depth[k] + 1u);
-            }
-            if (le.size() <= depth[k]) le.resize(depth[k] + 1u, 0u);
-            le[depth[k]] = k + 1u;
-        }
-    }
     c->stats[slot] = *st;
-    c->stats[slot].lds_resident = (uint32_t)stage_plan(c, c->h_img[slot]).mode;
-    return PPE_OK;
+    const int rc = plan_slot(c, slot);
+    c->stats[slot].lds_resident = c->plan[slot][0].mode;
+    return rc;
 }
 
-// One launch over batches in[0..nb) (nb <= PPE_MAX_BATCH, each n > 0): every wave takes its tiles of batch 0, then
-// of batch 1, ... (no barrier between batches, one image staging for all of them).
-int launch(ppe_ctx *c, const ppe_batch_t *in, const ppe_result_t *out, uint32_t nb, const ppe_cfg_t *cfg,
-           hipStream_t s, int slot_set, uint32_t idx_base = 0, const ppe_flowdev *fl = nullptr,
-           uint32_t *grid_out = nullptr) {
-    const int r = c->running;
-    const uint32_t words = (uint32_t)c->h_img[r].size();
-    const StagePlan plan = stage_plan(c, c->h_img[r], fl != nullptr);
-    const uint32_t wpb = plan.block / 64u;
-    ppe_kargs a;
-    std::memset(&a, 0, sizeof a);
-    uint32_t tiles = 0;
+// What the batches of one launch need of the grid and allow of the kernel variant
+struct BatchShape {
+    uint32_t tiles = 0;        // largest batch's tile count
     uint64_t tiles_total = 0;
-    bool part = true;  // the throughput layout in every batch (ppe_kargs.part_layout)
-    const bool use_ring = nb > PPE_MAX_BATCH;
-    int rslot = 0;
-    std::vector<ppe_bdesc> &rd = c->ring_tmp;
-    if (use_ring) {
-        if (nb > PPE_MAX_RING) return fail(c, PPE_EINVAL, "more than %d batches in one launch", PPE_MAX_RING);
-        rd.resize(nb);
-    }
+    bool part = true;          // the throughput layout in every batch (ppe_kargs.part_layout)
+};
+
+// The descriptors d[0..nb) of batches in / out [0..nb) (fl: a flow-table launch), over image slot r
+int fill_descs(ppe_ctx *c, int r, const ppe_batch_t *in, const ppe_result_t *out, uint32_t nb, uint32_t idx_base,
+               bool fl, ppe_bdesc *descs, BatchShape &sh) {
     for (uint32_t i = 0; i < nb; ++i) {
-        ppe_bdesc &d = use_ring ? rd[i] : a.batch[i];
+        ppe_bdesc &d = descs[i];
         d.hdr = in[i].hdr;
         d.len = in[i].len;
         d.ts = in[i].ts;
@@ -600,131 +405,93 @@ int launch(ppe_ctx *c, const ppe_batch_t *in, const ppe_result_t *out, uint32_t 
             d.verdict = (uint32_t *)out[i].packed;  // (the kernel writes the 8-B words through the verdict field)
             d.flags |= PPE_BD_PACKED;
         }
-        part = part && ((d.verdict && d.fhash && d.hit) || (d.flags & PPE_BD_PACKED)) && !d.tuple &&
-               ((d.fw_idx && d.fw_idx == d.drop_idx && !d.tile_cnt) || (d.flags & PPE_BD_PART8));
-        tiles = std::max(tiles, (in[i].n + 63u) / 64u);
-        tiles_total += (uint64_t)((in[i].n + 63u) / 64u);
+        sh.part = sh.part && ((d.verdict && d.fhash && d.hit) || (d.flags & PPE_BD_PACKED)) && !d.tuple &&
+                  ((d.fw_idx && d.fw_idx == d.drop_idx && !d.tile_cnt) || (d.flags & PPE_BD_PART8));
+        sh.tiles = std::max(sh.tiles, (in[i].n + 63u) / 64u);
+        sh.tiles_total += (uint64_t)((in[i].n + 63u) / 64u);
     }
+    return PPE_OK;
+}
+
+// The descriptor-ring slot a launch on stream s reads c->ring_tmp[0, nb) from.  A slot already holding exactly these
+// descriptors is reused as is (a dataplane cycling over a fixed set of batch buffers uploads its descriptor table
+// once); otherwise the next slot is rewritten once the launch that last read it (two ring launches ago) has completed
+int pick_ring_slot(ppe_ctx *c, uint32_t nb, hipStream_t s, int &rslot) {
+    const std::vector<ppe_bdesc> &rd = c->ring_tmp;
+    const size_t bytes = sizeof(ppe_bdesc) * nb;
     bool ring_copy = false;
-    if (use_ring) {
-        // a slot already holding exactly these descriptors is reused as is (a dataplane cycling over a fixed set of
-        // batch buffers uploads its descriptor table once); otherwise the next slot is rewritten once the launch
-        // that last read it (two ring launches ago) has completed
-        const size_t bytes = sizeof(ppe_bdesc) * nb;
-        rslot = -1;
-        for (int k = 0; k < 2; ++k)
-            if (c->ring_n[k] == nb && c->h_ring[k] && std::memcmp(c->h_ring[k], rd.data(), bytes) == 0) rslot = k;
-        if (rslot < 0) {
-            rslot = c->ring_next;
-            c->ring_next ^= 1;
-            for (auto &x : c->ring_readers[rslot]) {  // its last readers
-                const int rc = wait_reader(c, x);
-                if (rc != PPE_OK) return rc;
-            }
-            drop_readers(c->ring_readers[rslot]);
-            std::memcpy(c->h_ring[rslot], rd.data(), bytes);
-            c->ring_n[rslot] = nb;
-            HIPCHK(c, hipMemcpyAsync(c->d_ring[rslot], c->h_ring[rslot], bytes, hipMemcpyHostToDevice, s));
-            HIPCHK(c, hipEventRecord(c->ring_up[rslot], s));
-            c->ring_up_stream[rslot] = s;
-            ring_copy = true;
+    rslot = -1;
+    for (int k = 0; k < 2; ++k)
+        if (c->ring_n[k] == nb && c->h_ring[k] && std::memcmp(c->h_ring[k], rd.data(), bytes) == 0) rslot = k;
+    if (rslot < 0) {
+        rslot = c->ring_next;
+        c->ring_next ^= 1;
+        for (auto &x : c->ring_readers[rslot]) {  // its last readers
+            const int rc = wait_reader(c, x);
+            if (rc != PPE_OK) return rc;
         }
-        if (!ring_copy && c->ring_up_stream[rslot] != s && hipEventQuery(c->ring_up[rslot]) != hipSuccess)
-            HIPCHK(c, hipStreamWaitEvent(s, c->ring_up[rslot], 0));  // reused on another stream: after the upload only
-        a.batch[0] = rd[0];
+        drop_readers(c->ring_readers[rslot]);
+        std::memcpy(c->h_ring[rslot], rd.data(), bytes);
+        c->ring_n[rslot] = nb;
+        HIPCHK(c, hipMemcpyAsync(c->d_ring[rslot], c->h_ring[rslot], bytes, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipEventRecord(c->ring_up[rslot], s));
+        c->ring_up_stream[rslot] = s;
+        ring_copy = true;
+    }
+    if (!ring_copy && c->ring_up_stream[rslot] != s && hipEventQuery(c->ring_up[rslot]) != hipSuccess)
+        HIPCHK(c, hipStreamWaitEvent(s, c->ring_up[rslot], 0));  // reused on another stream: after the upload only
+    return PPE_OK;
+}
+
+// One launch over batches in[0..nb) (nb <= PPE_MAX_RING, each n > 0): every wave takes its tiles of batch 0, then
+// of batch 1, ... (no barrier between batches, one image staging for all of them).
+int launch(ppe_ctx *c, const ppe_batch_t *in, const ppe_result_t *out, uint32_t nb, const ppe_cfg_t *cfg,
+           hipStream_t s, int slot_set, uint32_t idx_base = 0, const ppe_flowdev *fl = nullptr,
+           uint32_t *grid_out = nullptr) {
+    const int r = c->running;
+    const ppe_plan &plan = c->plan[r][fl != nullptr];
+    ppe_kargs a;
+    std::memset(&a, 0, sizeof a);
+    const bool use_ring = nb > PPE_MAX_BATCH;
+    if (use_ring) {
+        if (nb > PPE_MAX_RING) return fail(c, PPE_EINVAL, "more than %d batches in one launch", PPE_MAX_RING);
+        c->ring_tmp.resize(nb);
+    }
+    BatchShape sh;
+    int rc = fill_descs(c, r, in, out, nb, idx_base, fl != nullptr, use_ring ? c->ring_tmp.data() : a.batch, sh);
+    if (rc != PPE_OK) return rc;
+    int rslot = 0;
+    if (use_ring) {
+        rc = pick_ring_slot(c, nb, s, rslot);
+        if (rc != PPE_OK) return rc;
+        a.batch[0] = c->ring_tmp[0];
         a.ring = c->d_ring[rslot];
     }
+    ppe_plan_apply(&a, &plan);
     a.nbatch = nb;
-    a.part_layout = (part && !fl && !env_int("PPE_NO_PART", 0)) ? 1u : 0u;
-    a.max_tiles = tiles;
-    // enough workgroups for every tile of every batch (the kernel splits its waves into batch groups), at most
-    // the resident grid
-    const uint32_t want = (uint32_t)std::min<uint64_t>((tiles_total + wpb - 1) / wpb, 1u << 30);
-    const uint32_t maxg = c->n_cu * blocks_per_cu(c, plan, fl != nullptr);
-    const uint32_t grid = std::max(1u, std::min(want, std::min(maxg, c->max_grid)));
+    a.max_tiles = sh.tiles;
+    a.part_layout = (sh.part && !fl && !env_int("PPE_NO_PART", 0)) ? 1u : 0u;
+    a.max_groups = ppe_pick_groups(nb, c->max_groups);
     a.img = c->d_img[r];
-    a.img_words = words;
     a.unsup_fw = cfg ? cfg->unsupport_proto_action : 0u;
     a.syn_check = cfg ? cfg->syn_check : 1u;
     a.now = cfg ? cfg->now_seconds : 0u;
-    a.default_action = c->h_img[r][PPE_IMG_W_DEFACT];
-    a.lds_words = plan.lds_words;
-    a.stage_src = plan.stage_src;
-    a.stage_words = plan.stage_words;
-    a.lds_blocks = plan.lds_blocks;
-    a.bsec_lds = plan.bsec_lds;
-    a.blk_lds = plan.blk_lds;
-    a.off_bsec = c->h_img[r][PPE_IMG_W_OFFBSEC];
-    a.off_blocks = c->h_img[r][PPE_IMG_W_OFFBLOCKS];
-    a.max_bdepth = c->h_img[r][PPE_IMG_W_MAXBDEPTH];
-    a.off_crec = c->h_img[r][PPE_IMG_W_OFFCREC];
-    a.off_idtab = c->h_img[r][PPE_IMG_W_OFFIDTAB];
-    a.crec_lds = plan.crec_lds;
-    a.idtab_lds = plan.idtab_lds;
-    if (plan.pipe == kPfCut) {  // (image v8 cut lists: header at PPE_IMG_W_OFFCUT)
-        const uint32_t *h = c->h_img[r].data() + c->h_img[r][PPE_IMG_W_OFFCUT];
-        a.cut = h[0];
-        a.cut_slc = h[4];
-        a.cut_ent = h[5];
-        a.cut_epl = h[7];
-        a.cut_div = h[10];
-        a.cut_idrel = (h[0] & PPE_CUT_LINES) ? 0u : 4u * (h[12] - h[5]);
-        a.cut_gbase = h[8];
-        a.cut_fp = h[9];
-        a.cut_gbase_lds = plan.cut_gbase_lds;
-        a.cut_fp_lds = plan.cut_fp_lds;
-        a.cut_ent_lds = plan.cut_ent_lds;
-    }
-    // batch groups: the kernel splits its waves into min(batches, max_groups) groups, group g taking batches g, g + G,
-    // ...; when G does not divide the batch count the last round leaves groups idle (20 batches at G = 8: the last
-    // 4 run on half the grid; C3 / C4 ring step +12 %, profiles/r3_ab_runs.md r4l).  Take the power-of-two G up to the
-    // cap (or the batch count itself when smaller) with the least work-slot time, ceil(batches / G) x G batch slots
-    // weighted by the per-batch cost of G groups (1 group 1.10, 2 groups 1.02, more 1.00: C1 per-batch 20.2 / 18.7 /
-    // 18.3 us at 1 / 2 / >= 4 groups); ties go to the larger G.  20 batches -> 4 groups, 32 -> 8, 33 -> 2.
-    {
-        const uint32_t gmax = std::max(1u, std::min(c->max_groups, nb));
-        auto cost = [&](uint32_t g) {
-            return (double)((nb + g - 1u) / g * g) * (g == 1u ? 1.10 : g == 2u ? 1.02 : 1.0);
-        };
-        uint32_t best = gmax;
-        double cbest = cost(gmax);
-        for (uint32_t g = 1u << (31 - __builtin_clz(gmax)); g >= 1u; g >>= 1) {
-            if (g == gmax) continue;
-            if (cost(g) < cbest - 1e-9) {
-                best = g;
-                cbest = cost(g);
-            }
-        }
-        a.max_groups = best;
-    }
-    a.max_depth = c->h_img[r][PPE_IMG_W_MAXDEPTH];
-    a.max_leaf = c->h_img[r][PPE_IMG_W_MAXLEAF];
-    a.root_ks = c->h_img[r][PPE_IMG_W_ROOTKS];
-    a.jump = c->h_img[r][PPE_IMG_W_JUMP];
-    a.off_nodes = c->h_img[r][PPE_IMG_W_OFFNODES];
-    if (plan.mode == 1) {
-        a.lds_iters = a.max_depth + 1u;
-    } else if (plan.mode == 2) {  // node reads 0..L-1 only visit depths < L: all inside the staged prefix
-        const std::vector<uint32_t> &le = c->level_end[r];
-        uint32_t L = 0;
-        while (L < le.size() && le[L] <= plan.lds_nodes) ++L;
-        a.lds_iters = std::min(L, a.max_depth + 1u);
-    }
-    a.off_leaf = c->h_img[r][PPE_IMG_W_OFFLEAF];
-    a.off_rules = c->h_img[r][PPE_IMG_W_OFFRULES];
-    a.off_resid = c->h_img[r][PPE_IMG_W_OFFRESID];
     a.cslots = c->d_cslots + (size_t)slot_set * c->max_grid * PPE_CSLOT_WORDS;
     a.sslots = c->d_sslots + (size_t)slot_set * c->max_grid * PPE_SSLOT_WORDS;
     a.stream = (c->stcp.track && !fl)
                    ? PPE_STM_TRACK | ((c->stcp.midstream | c->stcp.async_oneside) ? PPE_STM_PICKUP : 0u) : 0u;
     if (fl) a.flow = *fl;
+    // enough workgroups for every tile of every batch (the kernel splits its waves into batch groups), at most
+    // the resident grid
+    const uint32_t wpb = plan.block / 64u;
+    const uint32_t want = (uint32_t)std::min<uint64_t>((sh.tiles_total + wpb - 1) / wpb, 1u << 30);
+    const uint32_t maxg = c->n_cu * blocks_per_cu(c, r, fl != nullptr);
+    const uint32_t grid = std::max(1u, std::min(want, std::min(maxg, c->max_grid)));
     if (grid_out) *grid_out = grid;
 
+    // the timing events are taken before the launch takes its completion slot: nothing between track_launch and the
+    // launch call can return (a slot taken by a launch that never started would count as in flight for ever)
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    {
-        const int rc0 = track_launch(c, grid, a);
-        if (rc0 != PPE_OK) return rc0;
-    }
     if (c->timing) {
         if (c->ev_used + 2 > c->ev.size()) {
             for (int i = 0; i < 256; ++i) {
@@ -735,15 +502,16 @@ int launch(ppe_ctx *c, const ppe_batch_t *in, const ppe_result_t *out, uint32_t 
         }
         e0 = c->ev[c->ev_used];
         e1 = c->ev[c->ev_used + 1];
-        c->ev_used += 2;
     }
-    const int rc =
-        ppe_launch_classify(&a, grid, plan.mode, plan.pipe, (int)plan.block, fl != nullptr, (void *)s, (void *)e0,
-                            (void *)e1);
+    rc = track_launch(c, grid, a);
+    if (rc != PPE_OK) return rc;
+    rc = ppe_launch_classify(&a, grid, (int)plan.mode, (int)plan.pipe, (int)plan.block, fl != nullptr, (void *)s,
+                             (void *)e0, (void *)e1);
     if (rc != 0) {
         untrack_launch(c, grid, a);
         return fail(c, PPE_EIO, "kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
     }
+    if (c->timing) c->ev_used += 2;  // (only a launch that started: ppe_timing_read reads both events)
     // the launch reads its image slot (and ring slot): a later rewrite waits for its completion
     if (use_ring) note_launch_reader(c, c->ring_readers[rslot], s, a.done_seq);
     note_launch_reader(c, c->img_readers[r], s, a.done_seq);
@@ -1316,6 +1084,11 @@ int ppe_set_tuning(ppe_ctx_t *c, const ppe_tuning_t *t) {
     c->tune = *t;
     c->tune.pipeline = t->pipeline;
     c->tune.lds_image = t->lds_image ? 1u : 0u;
+    for (int r = 0; r < 2; ++r)
+        if (!c->h_img[r].empty()) {
+            const int rc = plan_slot(c, r);
+            if (rc != PPE_OK) return rc;
+        }
     return PPE_OK;
 }
 
@@ -1335,13 +1108,11 @@ int ppe_acl_image(ppe_ctx_t *c, uint32_t *words, uint32_t *n_words) {
 
 int ppe_launch_info(ppe_ctx_t *c, uint32_t *grid, uint32_t *block, uint32_t *lds_bytes, uint32_t *variant) {
     if (!c) return PPE_EINVAL;
-    const StagePlan plan = stage_plan(c, c->h_img[c->running]);
-    if (grid) *grid = std::min(c->n_cu * blocks_per_cu(c, plan), c->max_grid);
+    const ppe_plan &plan = c->plan[c->running][0];
+    if (grid) *grid = std::min(c->n_cu * blocks_per_cu(c, c->running), c->max_grid);
     if (block) *block = plan.block;
-    if (lds_bytes)
-        *lds_bytes = ppe_classify_fixed_lds((int)plan.block, plan.pipe, plan.mode) +
-                     (plan.mode ? ((plan.stage_words * 4u + 1023u) & ~1023u) : 0u);
-    if (variant) *variant = (uint32_t)plan.mode | ((uint32_t)plan.pipe << 4);
+    if (lds_bytes) *lds_bytes = plan.lds_bytes;
+    if (variant) *variant = plan.mode | (plan.pipe << 4);
     return PPE_OK;
 }
 

@@ -4,6 +4,8 @@
 
 #include <stdint.h>
 
+#include "ppe_hip.h"
+
 /* One batch of a launch: inputs, outputs (NULL = skipped) and sizes, as in ppe_batch_t / ppe_result_t. */
 struct ppe_bdesc {
     const uint8_t *hdr;
@@ -210,6 +212,43 @@ struct ppe_tuple_kargs {
     uint64_t now;
 };
 
+/* The classify kernel's variants (template parameters of ppe_classify_kernel; ppe_launch_info reports them as
+ * variant = image mode | tile fetch << 4).
+ * Image staging modes:
+ *   IMG_GLOBAL  the whole classifier image is read from global memory (L1/L2/MALL-cached)
+ *   IMG_LDS     the whole image is staged in LDS
+ *   IMG_SPLIT   a prefix [0, lds_words) is staged: header, the top of the BFS tree (every node of the first
+ *               lds_iters levels) and, when the prefix reaches them, the leaf lists and the rule records */
+#define IMG_GLOBAL 0
+#define IMG_LDS 1
+#define IMG_SPLIT 2
+/* PF: how a wave fetches and walks its tiles.  Register double-buffering (next tile's window, or only its first
+ * 16 B, requested before the current tile is processed) and an LDS-DMA next-tile pipeline were measured slower
+ * (DESIGN.md §7). */
+#define PF_NONE 0   /* one tile per wave, its window loaded at the top of its own iteration */
+#define PF_HOIST 1  /* as PF_NONE, but the first tile's loads are issued before the image staging (C1 21.7 us vs 22.2) */
+#define PF_MULTI 3  /* split / global images: each wave loads, decodes and walks PPE_MT tiles together
+                       (acl_walk_blocks_mt), 4 waves/SIMD with 128 VGPRs, one 1024-thread workgroup per CU and its
+                       whole LDS for the image */
+#define PF_CUT 5    /* images with cut lists (v7): one tile per wave (8 waves/SIMD), the keys in registers, the bucket
+                       groups in LDS, the list entries and ids in LDS (IMG_LDS) or from L2 (IMG_SPLIT) (acl_cut) */
+
+/* How one classifier image is launched under one tuning (csrc/launch_plan.cpp): the kernel variant, its LDS, and
+ * every kernel argument that depends on the image and the tuning only.  Computed once per image slot and tuning,
+ * never per launch.  Every field is a u32 (ppe/abi.py PLAN_FIELDS mirrors the order). */
+struct ppe_plan {
+    uint32_t mode;        /* IMG_* */
+    uint32_t pipe;        /* PF_* */
+    uint32_t block;       /* workgroup size */
+    uint32_t lds_bytes;   /* dynamic LDS of the launch (what ppe_launch_info reports for the stateless plan) */
+    /* ppe_kargs fields of the same names */
+    uint32_t img_words, default_action, lds_words, stage_src, stage_words, lds_blocks, bsec_lds, blk_lds;
+    uint32_t off_bsec, off_blocks, max_bdepth, off_crec, off_idtab, crec_lds, idtab_lds;
+    uint32_t cut, cut_slc, cut_gbase, cut_fp, cut_ent, cut_epl, cut_div, cut_idrel, cut_gbase_lds, cut_fp_lds,
+             cut_ent_lds;
+    uint32_t lds_iters, max_depth, max_leaf, root_ks, jump, off_nodes, off_leaf, off_rules, off_resid;
+};
+
 #define PPE_CSLOT_WORDS 32
 #define PPE_SSLOT_WORDS 8   /* PPE_SC__COUNT */
 #define PPE_STM_TRACK 1u
@@ -222,9 +261,17 @@ struct ppe_tuple_kargs {
 #ifdef __cplusplus
 extern "C" {
 #endif
-/* Launch the classify kernel. grid = workgroups (persistent), lds_img = stage image in LDS. Returns hipError_t. */
-/* mode: 0 image in global memory, 1 whole image in LDS, 2 prefix in LDS; pipe: 0 first tile loaded at the loop top,
- * 1 first tile's loads issued before the image staging (see ppe_kernels.hip) */
+/* csrc/launch_plan.cpp (host only: no HIP call, no context, no environment). */
+/* the plan of image words[0, n_words) under tuning t; flow != 0: for the flow-table classify kernel (built for the
+ * single-tile node walk only).  Returns PPE_OK, or PPE_EINVAL for what is no classifier image */
+int ppe_plan_image(const uint32_t *words, uint32_t n_words, const ppe_tuning_t *t, int flow,
+                   struct ppe_plan *out);
+/* the one place that copies a plan into kernel arguments */
+void ppe_plan_apply(struct ppe_kargs *a, const struct ppe_plan *p);
+/* batch groups (ppe_kargs.max_groups) of a launch over nbatch batches, at most max_groups */
+uint32_t ppe_pick_groups(uint32_t nbatch, uint32_t max_groups);
+
+/* Launch the classify kernel. grid = workgroups (persistent). Returns hipError_t.  mode: IMG_*, pipe: PF_* */
 int ppe_launch_classify(const struct ppe_kargs *a, uint32_t grid, int mode, int pipe, int block, int flow,
                         void *stream, void *ev_start, void *ev_stop);
 /* flow-table phases after a flow-mode classify launch (stream order): claim, resolve, finalize (+ revoke in its

@@ -437,14 +437,7 @@ __device__ __forceinline__ Dec decode(const uint32_t (&w)[13], uint32_t len32, c
     return k;
 }
 
-// Image staging modes:
-//   IMG_GLOBAL  the whole classifier image is read from global memory (L1/L2/MALL-cached)
-//   IMG_LDS     the whole image is staged in LDS
-//   IMG_SPLIT   a prefix [0, lds_words) is staged: header, the top of the BFS tree (every node of the first
-//               lds_iters levels) and, when the prefix reaches them, the leaf lists and the rule records
-#define IMG_GLOBAL 0
-#define IMG_LDS 1
-#define IMG_SPLIT 2
+// (image staging modes IMG_* and tile fetches PF_*: ppe_internal.h)
 
 // Classifier geometry for one launch (host-computed from the image header, ppe_image.h).
 struct AclGeo {
@@ -1278,13 +1271,6 @@ __device__ __forceinline__ uint32_t flow_find_claim(const ppe_flowdev &f, const 
     return PPE_FLOW_NONE;
 }
 
-// PF: how a wave fetches and walks its tiles
-#define PF_NONE 0   // one tile per wave, its window loaded at the top of its own iteration
-#define PF_HOIST 1  // as PF_NONE, but the first tile's loads are issued before the image staging
-#define PF_MULTI 3  // split / global images: each wave loads, decodes and walks PPE_MT tiles together (acl_walk_blocks_mt),
-                    // 4 waves/SIMD with 128 VGPRs, one 1024-thread workgroup per CU and its whole LDS for the image
-#define PF_CUT 5    // images with cut lists (v7): one tile per wave (8 waves/SIMD), the keys in registers, the bucket
-                    // groups in LDS, the list entries and ids in LDS (IMG_LDS) or from L2 (IMG_SPLIT) (acl_cut)
 #ifndef PPE_MT
 #define PPE_MT 4
 #endif
@@ -2395,7 +2381,7 @@ __global__ __launch_bounds__(PPE_BLOCK) void ppe_acl_tuple_kernel(ppe_tuple_karg
 #define PPE_DISPATCH_P(FN, M, ...)                                   \
     do {                                                             \
         if (pipe == PF_NONE) PPE_DISPATCH_B(FN, M, PF_NONE, __VA_ARGS__); \
-        if (pipe == PF_MULTI) PPE_DISPATCH_B(FN, M, PF_MULTI, __VA_ARGS__); \
+        if (pipe == PF_MULTI) return FN<M, PF_MULTI, 1024>(__VA_ARGS__); /* (planned at 1024 threads only) */ \
         if (pipe == PF_CUT) PPE_DISPATCH_B(FN, M, PF_CUT, __VA_ARGS__); \
         PPE_DISPATCH_B(FN, M, PF_HOIST, __VA_ARGS__);                \
     } while (0)

@@ -126,6 +126,23 @@ class Tuning(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+# struct ppe_plan (csrc/ppe_internal.h): how one classifier image is launched under one tuning; every field a u32
+PLAN_FIELDS = ["mode", "pipe", "block", "lds_bytes",
+               "img_words", "default_action", "lds_words", "stage_src", "stage_words", "lds_blocks", "bsec_lds",
+               "blk_lds", "off_bsec", "off_blocks", "max_bdepth", "off_crec", "off_idtab", "crec_lds", "idtab_lds",
+               "cut", "cut_slc", "cut_gbase", "cut_fp", "cut_ent", "cut_epl", "cut_div", "cut_idrel", "cut_gbase_lds",
+               "cut_fp_lds", "cut_ent_lds",
+               "lds_iters", "max_depth", "max_leaf", "root_ks", "jump", "off_nodes", "off_leaf", "off_rules",
+               "off_resid"]
+
+
+class Plan(C.Structure):
+    _fields_ = [(name, C.c_uint32) for name in PLAN_FIELDS]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k in PLAN_FIELDS}
+
+
 class FlowInfo(C.Structure):
     _fields_ = [("live", C.c_uint64), ("new_flow", C.c_uint64), ("del_flow", C.c_uint64), ("capacity", C.c_uint32),
                 ("max_batch", C.c_uint32), ("slots", C.c_uint32), ("tombstones", C.c_uint32), ("rehashes", C.c_uint32),
@@ -229,6 +246,8 @@ EXPORTS = [
     "ppe_defrag_last_error",
     "ppe_stream_tcp_set", "ppe_stream_tcp_get", "ppe_stream_counters_read", "ppe_stream_counters_clear",
     "ppe_format_tcpstream_stat",
+    # csrc/ppe_internal.h: the host-only launch planner (internal helpers, not part of the public headers)
+    "ppe_plan_image", "ppe_pick_groups",
     # ppe_acl.h
     "ppe_rule_list_init", "ppe_rule_list_free", "Rule_add", "Rule_del_by_id", "Rule_del_all",
     "Rule_duplicate_check", "Rule_Load_Line", "ppe_rule_load_file", "DP_Acl_Rule_Init", "DP_Acl_Load_Rule",
@@ -332,6 +351,8 @@ def _open(p: Path, mode, strict: bool = True) -> C.CDLL:
         "ppe_stream_counters_clear": ([vp], C.c_int),
         "ppe_format_tcpstream_stat": ([C.POINTER(StreamCounters), C.POINTER(StreamTcpCfg), C.c_char_p, C.c_size_t],
                                       C.c_int),
+        "ppe_plan_image": ([vp, u32, C.POINTER(Tuning), C.c_int, C.POINTER(Plan)], C.c_int),
+        "ppe_pick_groups": ([u32, u32], u32),
         "ppe_rule_list_init": ([], C.c_int),
         "ppe_rule_list_free": ([], None),
         "Rule_add": ([vp, C.POINTER(u32)], C.c_int),
