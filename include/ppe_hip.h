@@ -39,7 +39,8 @@ extern "C" {
  * 5: the tuple carries a fragment's Defrag fields and the option-past-the-window bit; strides 64..256;
  * 6: ppe_acl_stats_t cut fields; 7: ppe_rules_stage / _publish; 8: ppe_result_t.packed (8-B verdict + flow hash +
  * ACL hit); additive within 8 (no existing struct or value changes): the StreamTcp first-packet verdict
- * (ppe_stream_tcp_*, statuses 20-23, ppe_stream_counters_*, ppe_format_tcpstream_stat), off until set */
+ * (ppe_stream_tcp_*, statuses 20-23, ppe_stream_counters_*, ppe_format_tcpstream_stat), off until set; the port-scan
+ * detector (ppe_portscan_*, status 24, ppe_format_pkt_stat_ps, ppe_format_fw_config), off until a table is attached */
 #define PPE_ABI_VERSION 8
 
 /* error codes (negative return values) */
@@ -80,7 +81,14 @@ enum ppe_status {
     PPE_ST_STREAM_FIN_NO_SESSION = 21,        /* FIN                        STREAM_FIN_BUT_NO_SESSION  stream-tcp.c:249-254 */
     PPE_ST_STREAM_MIDSTREAM_ONESIDE_OFF = 22, /* SYN|ACK, midstream and async_oneside both 0           stream-tcp.c:255-261 */
     PPE_ST_STREAM_MIDSTREAM_OFF = 23,         /* ACK without SYN, midstream 0                           stream-tcp.c:364-370 */
-    PPE_ST__COUNT = 24
+    /* PortScan_Detect (dataplane/src/attack/dp_portscan.c:231-272) answered NOMEM, DETECTED or HOLD with
+     * portscan_action 0, only with a table attached (ppe_portscan_attach): STAT_ATTACK_PORTSCAN_DROP and return NULL
+     * before the ACL (flow.c:216-230), so acl_hit is -1 and PPE_F_ACL clear; flow hash, tuple and other flags stay. */
+    PPE_ST_PORTSCAN_DROP = 24,
+    /* PPE_ST__COUNT keeps its value: the statuses a context without a port-scan table produces (0-23; bindings and
+     * tables sized by it stay valid).  PPE_ST__END counts every status, PPE_ST_PORTSCAN_DROP included. */
+    PPE_ST__COUNT = 24,
+    PPE_ST__END = 25
 };
 
 enum ppe_action { PPE_ACT_FW = 0, PPE_ACT_DROP = 1, PPE_ACT_PUNT = 2 };
@@ -506,6 +514,72 @@ int  ppe_defrag_age(ppe_defrag_t *d, uint64_t now_seconds, uint64_t timeout_seco
                     uint32_t max, uint32_t *n_dropped, uint32_t *n_freed);
 int  ppe_defrag_info(ppe_defrag_t *d, ppe_defrag_info_t *info);      /* synchronises */
 
+/* ---- Port-scan detector on the stateless classify path (dataplane/src/attack/dp_portscan.c) ----
+ * The reference runs PortScan_Detect on every flow miss after syn_check and before the ACL (flow.c:215-230).  The
+ * stateless path treats every packet as a miss, so with a table attached and able = 1, ppe_classify and
+ * ppe_classify_batches run the detector for every packet that would reach the ACL (PPE_F_L4 set and not stopped by
+ * syn_check), in batch index order, batches in call order (the batches of one ppe_classify_batches call count as
+ * consecutive batches), with exactly the sequential semantics of one core:
+ *   find the source's record by sip or create it (zeroed; a failed create, `capacity` records live, is NOMEM:
+ *   the first capacity - live new sources by first appearance get records, every packet of the others is NOMEM);
+ *   both set cycle = now_cycles (:109, :263); then PortScan_Detec_process (:139-210) verbatim: the hold test against
+ *   mbuf->timestamp (batch.ts[i], or cfg->now_seconds without ts), last_dport == 0 as "first create", the three
+ *   unsigned now - last_cycle branches (< rate; strictly between rate and 2 rate; everything else, which includes
+ *   exactly rate, exactly 2 rate and a wrapped now < last_cycle), detection when last_exception >= exception_freq on
+ *   a port change (hold = now_seconds + hold_seconds).
+ * Any result but OK with action 0 makes the packet PPE_ST_PORTSCAN_DROP: FLOW_PROC_FAIL and OUT_DROP, no ACL counter,
+ * no StreamTcp.  With action 1 the packet goes on to the ACL unchanged; detection and state still run.
+ * The clock is the caller's: ppe_portscan_clock sets cvmx_get_cycle() and OCT_TIME_SECONDS_SINCE1970 for the batches
+ * enqueued after it (by value, no synchronisation); rate (oct_cpu_rate) is cycles_per_second.
+ * With a table attached and able = 1 every classify call of the context must go through one stream (or be ordered by
+ * the caller), and ppe_classify_flow and ppe_classify_host return PPE_ENOTSUP before touching anything (the first:
+ * whether a packet is a miss depends on earlier packets' verdicts; the second: its chunks run on several streams).
+ * A new context has nothing attached: every output and counter is as without this interface. */
+typedef struct {
+    uint32_t able;               /* portscan_able (dp_portscan.c:10); 0/1                                         */
+    uint32_t action;             /* portscan_action (:11): 0 drop, 1 forward                                       */
+    uint32_t exception_freq;     /* portscan_exception_freq (:9)                                                   */
+    uint32_t hold_seconds;       /* flood_hold_time (dp_attack.c:25)                                               */
+    uint32_t capacity;           /* record pool; 0 = PORTSCAN_ITEM_NUM 100000 (dp_portscan.h:67)                    */
+    uint32_t max_batch;          /* packets per batch; 0 = 1 << 20                                                 */
+    uint64_t cycles_per_second;  /* oct_cpu_rate; 0 = 1000000000                                                   */
+    uint64_t pad;
+} ppe_portscan_cfg_t;
+
+typedef struct {                 /* pcb_t (dp_portscan.h:25-35)                                                     */
+    uint32_t sip;
+    uint32_t last_dport;
+    uint32_t exception, last_exception;
+    uint64_t last_cycle, cycle, hold;
+} ppe_portscan_entry_t;
+
+typedef struct {
+    uint64_t live;               /* records in use                                                                 */
+    uint64_t new_pcb, del_pcb;   /* dp_portscan.c:12-13                                                            */
+    uint64_t ok, nomem, detected, hold;   /* packets per PortScan_Detect result                                    */
+    uint64_t drop;               /* attstat.portscan_drop (STAT_ATTACK_PORTSCAN_DROP, flow.c:226)                   */
+    ppe_portscan_cfg_t cfg;      /* the configuration in force (defaults filled in)                                */
+    uint32_t slots, rebuilds;    /* open-addressing slots; table rebuilds (aging, slot reclamation)                */
+} ppe_portscan_info_t;
+
+typedef struct ppe_portscan_table ppe_portscan_t;
+/* PortScan_Module_init (dp_portscan.c:308-356).  cfg NULL = the reference defaults {1, 0, 50, 600, 0, 0, 0};
+ * able / action above 1: PPE_EINVAL. */
+int  ppe_portscan_create(ppe_ctx_t *ctx, const ppe_portscan_cfg_t *cfg, ppe_portscan_t **out);
+int  ppe_portscan_destroy(ppe_portscan_t *ps);   /* detaches it from its context first */
+int  ppe_portscan_attach(ppe_ctx_t *ctx, ppe_portscan_t *ps);   /* NULL detaches */
+int  ppe_portscan_clock(ppe_portscan_t *ps, uint64_t now_cycles, uint64_t now_seconds);
+/* able, action, exception_freq, hold_seconds live (dp_cmd.c:2133-2236); the other words are ignored */
+int  ppe_portscan_set(ppe_portscan_t *ps, const ppe_portscan_cfg_t *cfg);
+/* PortScan_timeout (:43-93): free every record with now > cycle && now - cycle > 20 * rate; *freed may be NULL.
+ * Synchronises. */
+int  ppe_portscan_age(ppe_portscan_t *ps, uint64_t now_cycles, uint64_t *freed);
+int  ppe_portscan_info(ppe_portscan_t *ps, ppe_portscan_info_t *info);   /* synchronises */
+/* Copy up to `max` records to host (table order); *n = records in use.  Synchronises. */
+int  ppe_portscan_dump(ppe_portscan_t *ps, ppe_portscan_entry_t *entries, uint32_t max, uint32_t *n);
+const char *ppe_portscan_last_error(ppe_portscan_t *ps);
+
+
 /* `show packet statistic` / `show flow statistic` text (dp_show_pkt_stat / dp_show_flow_stat,
  * dataplane/src/common/dp_cmd.c:844-1818, 2346-2392) into buf (NUL-terminated, truncated to cap); returns the full
  * length.  The _ex forms take the IPv4 reassembly table's counters (NULL: those lines print 0, as the plain forms
@@ -516,6 +590,12 @@ int  ppe_format_flow_stat(const ppe_flow_info_t *f, char *buf, size_t cap);
 int  ppe_format_pkt_stat_ex(const ppe_counters_t *c, const ppe_defrag_info_t *df, int teardrop_monitor, char *buf,
                             size_t cap);
 int  ppe_format_flow_stat_ex(const ppe_flow_info_t *f, const ppe_defrag_info_t *df, char *buf, size_t cap);
+/* ppe_format_pkt_stat_ex with the attack section's portscan_drop line from ps_info->drop (NULL: 0, as _ex prints) */
+int  ppe_format_pkt_stat_ps(const ppe_counters_t *c, const ppe_defrag_info_t *df, int teardrop_monitor,
+                            const ppe_portscan_info_t *ps_info, char *buf, size_t cap);
+/* the four port-scan lines of `show fw config` (dp_cmd.c:2578-2590): detect stat, detect action, flood hold time,
+ * portscan_exception_freq.  cfg NULL = the reference defaults. */
+int  ppe_format_fw_config(const ppe_portscan_cfg_t *cfg, char *buf, size_t cap);
 const char *ppe_defrag_last_error(ppe_defrag_t *d);
 
 /* Human-readable last error of this context (static storage of the ctx). */

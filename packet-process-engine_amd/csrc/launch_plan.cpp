@@ -310,4 +310,8 @@ uint32_t ppe_pick_groups(uint32_t nb, uint32_t max_groups) {
     return best;
 }
 
+uint32_t ppe_pick_portscan(int flow, int attached, uint32_t able) {
+    return (!flow && attached && able == 1u) ? 1u : 0u;  // portscan_able != 1: DECODE_OK at once (dp_portscan.c:238-241)
+}
+
 }  // extern "C"

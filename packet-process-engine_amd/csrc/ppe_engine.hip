@@ -111,6 +111,22 @@ struct Reader {
 };
 constexpr uint32_t kDoneSlots = 4096;  // launch-completion slots (sequence numbers modulo this)
 
+// ppe_portscan_create: the port-scan detector's table and batch scratch (csrc/ppe_portscan.hip)
+struct ppe_portscan_table {
+    ppe_ctx *ctx = nullptr;
+    ppe_portscan_cfg_t cfg = {};
+    uint64_t now_cycles = 0, now_seconds = 0;   // ppe_portscan_clock
+    unsigned long long *keys = nullptr, *recs = nullptr, *ctl = nullptr;
+    uint32_t nslots = 0, npad_max = 0, rebuilds = 0;
+    uint64_t occ_ub = 0;          // upper bound of the keys in use (the last count read + packets enqueued since)
+    uint32_t *slot_of = nullptr, *dport = nullptr, *cbase = nullptr, *work = nullptr;
+    uint64_t *pts = nullptr;
+    unsigned long long *skey = nullptr, *cmask = nullptr, *mask = nullptr;
+    uint8_t *res = nullptr;
+    size_t mask_cap = 0;          // words of `mask`: the drop masks of the batches of one launch
+    char err[256] = {0};
+};
+
 struct ppe_ctx {
     int device = 0;
     uint32_t n_cu = 256;
@@ -166,6 +182,7 @@ struct ppe_ctx {
     // setups, but more batches streamed at once (DRAM locality); C1, 20-32 batches per launch, per batch: 1 / 2 / 4
     // / 8 / 32 groups 20.2 / 18.7 / 18.3 / 18.3 / 19.1 us (one run, tools/ab_bench.py)
     uint32_t max_groups = 8;
+    ppe_portscan_table *ps = nullptr;  // ppe_portscan_attach
     FlowTable *flow = nullptr;  // ppe_flow_create
     LookupStage lk;             // ppe_acl_lookup_host
     uint32_t *d_steer = nullptr;  // ppe_steer_partition: per-tile owner counts / offsets
@@ -372,7 +389,8 @@ struct BatchShape {
 
 // The descriptors d[0..nb) of batches in / out [0..nb) (fl: a flow-table launch), over image slot r
 int fill_descs(ppe_ctx *c, int r, const ppe_batch_t *in, const ppe_result_t *out, uint32_t nb, uint32_t idx_base,
-               bool fl, ppe_bdesc *descs, BatchShape &sh) {
+               bool fl, ppe_bdesc *descs, BatchShape &sh, bool psc = false) {
+    uint32_t ps_off = 0;  // port-scan launches: the batches' drop masks lie one after the other (ps_prepass)
     for (uint32_t i = 0; i < nb; ++i) {
         ppe_bdesc &d = descs[i];
         d.hdr = in[i].hdr;
@@ -407,6 +425,10 @@ int fill_descs(ppe_ctx *c, int r, const ppe_batch_t *in, const ppe_result_t *out
         }
         sh.part = sh.part && ((d.verdict && d.fhash && d.hit) || (d.flags & PPE_BD_PACKED)) && !d.tuple &&
                   ((d.fw_idx && d.fw_idx == d.drop_idx && !d.tile_cnt) || (d.flags & PPE_BD_PART8));
+        if (psc) {
+            d.flags |= ps_off << PPE_BD_PSOFF_SHIFT;
+            ps_off += (in[i].n + 63u) / 64u;
+        }
         sh.tiles = std::max(sh.tiles, (in[i].n + 63u) / 64u);
         sh.tiles_total += (uint64_t)((in[i].n + 63u) / 64u);
     }
@@ -443,6 +465,148 @@ int pick_ring_slot(ppe_ctx *c, uint32_t nb, hipStream_t s, int &rslot) {
     return PPE_OK;
 }
 
+int ps_fail(ppe_portscan_table *t, int code, const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(t->err, sizeof t->err, fmt, ap);
+    va_end(ap);
+    if (t->ctx) std::snprintf(t->ctx->err, sizeof t->ctx->err, "%s", t->err);
+    return code;
+}
+#define PSCHK(t, expr)                                                                               \
+    do {                                                                                             \
+        hipError_t e_ = (hipError_t)(expr);                                                          \
+        if (e_ != hipSuccess) return ps_fail((t), PPE_EIO, "%s: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+
+void ps_table_args(const ppe_portscan_table &t, ppe_ps_kargs &a) {
+    std::memset(&a, 0, sizeof a);
+    a.keys = t.keys;
+    a.recs = t.recs;
+    a.ctl = t.ctl;
+    a.smask = t.nslots - 1u;
+    a.capacity = t.cfg.capacity;
+    a.rate = t.cfg.cycles_per_second;
+    a.n = 1;
+    a.npad = PPE_PS_SORT_BLOCK;
+}
+
+// Move the records that stay into an empty table: aging (age != 0: PortScan_timeout at now_cycles) and the
+// reclamation of slots whose source never got a record.  Synchronises.
+int ps_rebuild(ppe_portscan_table *t, int age, uint64_t now_cycles) {
+    const size_t kb = (size_t)t->nslots * 8u, rb = kb * PPE_PS_REC_WORDS;
+    unsigned long long *nk = nullptr, *nr = nullptr;
+    if (hipMalloc(&nk, kb) != hipSuccess || hipMalloc(&nr, rb) != hipSuccess) {
+        (void)hipFree(nk);
+        return ps_fail(t, PPE_ENOMEM, "port-scan table rebuild: out of device memory");
+    }
+    ppe_ps_kargs a;
+    ps_table_args(*t, a);
+    a.dkeys = nk;
+    a.drecs = nr;
+    a.dmask = a.smask;
+    a.age = age ? 1u : 0u;
+    a.now_cycles = now_cycles;
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemset(nk, 0, kb);
+    if (e == hipSuccess) e = hipMemset(nr, 0, rb);
+    if (e == hipSuccess) e = (hipError_t)ppe_launch_portscan(PPE_PS_K_REBUILD, &a, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    unsigned long long live = 0;
+    if (e == hipSuccess) e = hipMemcpy(&live, t->ctl + PPE_PSC_LIVE, 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(t->ctl + PPE_PSC_OCC, &live, 8, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(nk);
+        (void)hipFree(nr);
+        return ps_fail(t, PPE_EIO, "port-scan table rebuild: %s", hipGetErrorString(e));
+    }
+    (void)hipFree(t->keys);
+    (void)hipFree(t->recs);
+    t->keys = nk;
+    t->recs = nr;
+    t->occ_ub = live;
+    ++t->rebuilds;
+    return PPE_OK;
+}
+
+// PortScan_Detect for batches in[0, nb) in order on stream s (csrc/ppe_portscan.hip), their drop masks one after the
+// other in t->mask
+int ps_prepass(ppe_ctx *c, const ppe_batch_t *in, uint32_t nb, const ppe_cfg_t *cfg, hipStream_t s) {
+    ppe_portscan_table *t = c->ps;
+    size_t words = 0;
+    for (uint32_t i = 0; i < nb; ++i) {
+        if (in[i].n > t->cfg.max_batch)
+            return fail(c, PPE_EINVAL, "batch of %u packets exceeds the port-scan table's max_batch %u", in[i].n,
+                        t->cfg.max_batch);
+        words += (in[i].n + 63u) / 64u;
+    }
+    if (words > t->mask_cap) {  // (grows only: the masks of a launch over many batches)
+        PSCHK(t, hipDeviceSynchronize());
+        (void)hipFree(t->mask);
+        t->mask = nullptr;
+        t->mask_cap = 0;
+        PSCHK(t, hipMalloc(&t->mask, words * 8u));
+        t->mask_cap = words;
+    }
+    size_t off = 0;
+    for (uint32_t i = 0; i < nb; ++i) {
+        const uint32_t n = in[i].n;
+        // keys in use never reach 3/4 of the slots: the bound first, then the count, then a rebuild without aging
+        if (t->occ_ub + n > (uint64_t)t->nslots / 4u * 3u) {
+            PSCHK(t, hipDeviceSynchronize());
+            unsigned long long occ = 0;
+            PSCHK(t, hipMemcpy(&occ, t->ctl + PPE_PSC_OCC, 8, hipMemcpyDeviceToHost));
+            t->occ_ub = occ;
+            if (t->occ_ub + n > (uint64_t)t->nslots / 4u * 3u) {
+                const int rc = ps_rebuild(t, 0, 0);
+                if (rc != PPE_OK) return rc;
+            }
+        }
+        t->occ_ub += n;
+        ppe_ps_kargs a;
+        ps_table_args(*t, a);
+        a.hdr = in[i].hdr;
+        a.len = in[i].len;
+        a.ts = in[i].ts;
+        a.n = n;
+        a.stride = in[i].stride;
+        a.syn_check = cfg ? cfg->syn_check : 1u;
+        a.ts_default = cfg ? cfg->now_seconds : 0u;
+        uint32_t npad = PPE_PS_SORT_BLOCK;
+        while (npad < n) npad <<= 1;
+        a.npad = npad;
+        a.now_cycles = t->now_cycles;
+        a.now_seconds = t->now_seconds;
+        a.freq = t->cfg.exception_freq;
+        a.hold_seconds = t->cfg.hold_seconds;
+        a.action = t->cfg.action;
+        a.slot_of = t->slot_of;
+        a.dport = t->dport;
+        a.pts = t->pts;
+        a.skey = t->skey;
+        a.res = t->res;
+        a.cmask = t->cmask;
+        a.cbase = t->cbase;
+        a.work = t->work;
+        a.mask = t->mask + off;
+        off += (n + 63u) / 64u;
+        static const int pre[] = {PPE_PS_K_FIND, PPE_PS_K_CREATORS, PPE_PS_K_SCAN, PPE_PS_K_GRANT, PPE_PS_K_KEYS,
+                                  PPE_PS_K_SORT_LDS};
+        for (int k : pre) PSCHK(t, ppe_launch_portscan(k, &a, s));
+        for (uint32_t k = 2u * PPE_PS_SORT_BLOCK; k <= npad && k; k <<= 1) {
+            a.sort_k = k;
+            for (uint32_t j = k >> 1; j >= PPE_PS_SORT_BLOCK; j >>= 1) {
+                a.sort_j = j;
+                PSCHK(t, ppe_launch_portscan(PPE_PS_K_SORT_GLOBAL, &a, s));
+            }
+            PSCHK(t, ppe_launch_portscan(PPE_PS_K_SORT_MERGE_LDS, &a, s));
+        }
+        static const int post[] = {PPE_PS_K_HEADS, PPE_PS_K_MEMBERS, PPE_PS_K_WALK, PPE_PS_K_MASK};
+        for (int k : post) PSCHK(t, ppe_launch_portscan(k, &a, s));
+    }
+    return PPE_OK;
+}
+
 // One launch over batches in[0..nb) (nb <= PPE_MAX_RING, each n > 0): every wave takes its tiles of batch 0, then
 // of batch 1, ... (no barrier between batches, one image staging for all of them).
 int launch(ppe_ctx *c, const ppe_batch_t *in, const ppe_result_t *out, uint32_t nb, const ppe_cfg_t *cfg,
@@ -458,8 +622,14 @@ int launch(ppe_ctx *c, const ppe_batch_t *in, const ppe_result_t *out, uint32_t 
         c->ring_tmp.resize(nb);
     }
     BatchShape sh;
-    int rc = fill_descs(c, r, in, out, nb, idx_base, fl != nullptr, use_ring ? c->ring_tmp.data() : a.batch, sh);
+    const bool psc = ppe_pick_portscan(fl != nullptr, c->ps != nullptr, c->ps ? c->ps->cfg.able : 0u) != 0u;
+    int rc = fill_descs(c, r, in, out, nb, idx_base, fl != nullptr, use_ring ? c->ring_tmp.data() : a.batch, sh, psc);
     if (rc != PPE_OK) return rc;
+    if (psc) {  // PortScan_Detect for every batch, in order, ahead of the launch on its stream
+        rc = ps_prepass(c, in, nb, cfg, s);
+        if (rc != PPE_OK) return rc;
+        a.psmask = c->ps->mask;
+    }
     int rslot = 0;
     if (use_ring) {
         rc = pick_ring_slot(c, nb, s, rslot);
@@ -735,6 +905,24 @@ int ppe_classify_batches(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t
             }
         return launch(c, gin.data(), gout.data(), nonempty, cfg, s, 0);
     }
+    if (c->ps && c->ps->cfg.able == 1u) {
+        // the detector takes the batches in call order: the launches go one after the other on the caller's stream
+        std::vector<ppe_batch_t> gin;
+        std::vector<ppe_result_t> gout;
+        for (uint32_t i = 0; i <= nbatch; ++i) {
+            if (i < nbatch && in[i].n) {
+                gin.push_back(in[i]);
+                gout.push_back(out[i]);
+            }
+            if (gin.size() == per || (i == nbatch && !gin.empty())) {
+                const int rc = launch(c, gin.data(), gout.data(), (uint32_t)gin.size(), cfg, s, 0);
+                if (rc != PPE_OK) return rc;
+                gin.clear();
+                gout.clear();
+            }
+        }
+        return PPE_OK;
+    }
     if (!c->pipe[0]) {
         for (int k = 0; k < kPipeStreams; ++k)
             HIPCHK(c, hipStreamCreateWithFlags(&c->pipe[k], mode == 2 ? hipStreamDefault : hipStreamNonBlocking));
@@ -789,6 +977,8 @@ static const void *mapped_host(const void *p) {
 int ppe_classify_host(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *out, const ppe_cfg_t *cfg,
                       uint32_t chunk) {
     if (!c || !out) return PPE_EINVAL;
+    // the chunks of the staged path run on several streams; the detector needs the packets in order on one
+    if (c->ps) return fail(c, PPE_ENOTSUP, "ppe_classify_host with a port-scan table attached is not supported");
     int rc = check_batch(c, in, cfg);
     if (rc != PPE_OK || in->n == 0) return rc;
     HIPCHK(c, hipSetDevice(c->device));
@@ -1048,6 +1238,158 @@ int ppe_stream_counters_clear(ppe_ctx_t *c) {
                         (size_t)kSlotSets * c->max_grid * PPE_SSLOT_WORDS * sizeof(unsigned long long)));
     return PPE_OK;
 }
+
+// ---- port-scan detector (dataplane/src/attack/dp_portscan.c) ----
+static void ps_free(ppe_portscan_table *t) {
+    void *ptrs[] = {t->keys, t->recs, t->ctl, t->slot_of, t->dport, t->cbase, t->work, t->pts, t->skey, t->cmask,
+                    t->mask, t->res};
+    for (void *p : ptrs)
+        if (p) (void)hipFree(p);
+    delete t;
+}
+
+static int ps_check_words(const ppe_portscan_cfg_t &v) { return (v.able > 1u || v.action > 1u) ? PPE_EINVAL : PPE_OK; }
+
+int ppe_portscan_create(ppe_ctx_t *c, const ppe_portscan_cfg_t *cfg, ppe_portscan_t **out) {
+    if (!c || !out) return PPE_EINVAL;
+    *out = nullptr;
+    // portscan_able 1, portscan_action 0, portscan_exception_freq 50 (dp_portscan.c:9-11), flood_hold_time 600
+    // (dp_attack.c:25)
+    ppe_portscan_cfg_t v = {1u, 0u, 50u, 600u, 0u, 0u, 0u, 0u};
+    if (cfg) v = *cfg;
+    if (ps_check_words(v) != PPE_OK) return fail(c, PPE_EINVAL, "ppe_portscan_create: able and action must be 0/1");
+    if (v.capacity == 0) v.capacity = 100000u;  // PORTSCAN_ITEM_NUM (dp_portscan.h:67)
+    if (v.max_batch == 0) v.max_batch = 1u << 20;
+    if (v.cycles_per_second == 0) v.cycles_per_second = 1000000000ull;
+    v.pad = 0;
+    if (v.capacity > (1u << 28) || v.max_batch > (1u << 28))
+        return fail(c, PPE_EINVAL, "ppe_portscan_create: capacity / max_batch too large");
+    HIPCHK(c, hipSetDevice(c->device));
+    ppe_portscan_table *t = new ppe_portscan_table;
+    t->ctx = c;
+    t->cfg = v;
+    uint32_t ns = 1024;
+    while (ns < 2u * (v.capacity + v.max_batch)) ns <<= 1;
+    t->nslots = ns;
+    uint32_t npad = PPE_PS_SORT_BLOCK;
+    while (npad < v.max_batch) npad <<= 1;
+    t->npad_max = npad;
+    const size_t m = v.max_batch, tiles = (m + 63u) / 64u;
+    bool ok = hipMalloc(&t->keys, (size_t)ns * 8u) == hipSuccess &&
+              hipMalloc(&t->recs, (size_t)ns * 8u * PPE_PS_REC_WORDS) == hipSuccess &&
+              hipMalloc(&t->ctl, PPE_PSC_WORDS * 8u) == hipSuccess && hipMalloc(&t->slot_of, m * 4u) == hipSuccess &&
+              hipMalloc(&t->dport, m * 4u) == hipSuccess && hipMalloc(&t->cbase, tiles * 4u) == hipSuccess &&
+              hipMalloc(&t->work, m * 4u) == hipSuccess && hipMalloc(&t->pts, m * 8u) == hipSuccess &&
+              hipMalloc(&t->skey, (size_t)npad * 8u) == hipSuccess && hipMalloc(&t->cmask, tiles * 8u) == hipSuccess &&
+              hipMalloc(&t->mask, tiles * 8u) == hipSuccess && hipMalloc(&t->res, m) == hipSuccess;
+    t->mask_cap = ok ? tiles : 0;
+    ok = ok && hipMemset(t->keys, 0, (size_t)ns * 8u) == hipSuccess &&
+         hipMemset(t->recs, 0, (size_t)ns * 8u * PPE_PS_REC_WORDS) == hipSuccess &&
+         hipMemset(t->ctl, 0, PPE_PSC_WORDS * 8u) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        ps_free(t);
+        return fail(c, PPE_ENOMEM, "ppe_portscan_create: out of device memory");
+    }
+    *out = t;
+    return PPE_OK;
+}
+
+int ppe_portscan_destroy(ppe_portscan_t *t) {
+    if (!t) return PPE_EINVAL;
+    (void)hipSetDevice(t->ctx->device);
+    (void)hipDeviceSynchronize();
+    if (t->ctx->ps == t) t->ctx->ps = nullptr;
+    ps_free(t);
+    return PPE_OK;
+}
+
+int ppe_portscan_attach(ppe_ctx_t *c, ppe_portscan_t *t) {
+    if (!c) return PPE_EINVAL;
+    if (t && t->ctx != c) return fail(c, PPE_EINVAL, "ppe_portscan_attach: the table belongs to another context");
+    c->ps = t;
+    return PPE_OK;
+}
+
+int ppe_portscan_clock(ppe_portscan_t *t, uint64_t now_cycles, uint64_t now_seconds) {
+    if (!t) return PPE_EINVAL;
+    t->now_cycles = now_cycles;  // by value into the kernel arguments of the batches enqueued from now on
+    t->now_seconds = now_seconds;
+    return PPE_OK;
+}
+
+int ppe_portscan_set(ppe_portscan_t *t, const ppe_portscan_cfg_t *cfg) {
+    if (!t || !cfg) return PPE_EINVAL;
+    if (ps_check_words(*cfg) != PPE_OK) return ps_fail(t, PPE_EINVAL, "ppe_portscan_set: able and action must be 0/1");
+    t->cfg.able = cfg->able;                      // dp_portscan_able_set, dp_cmd.c:2141-2145
+    t->cfg.action = cfg->action;                  // dp_portscan_action_set, :2203-2207
+    t->cfg.exception_freq = cfg->exception_freq;  // dp_portscan_freq_set, :2239-2243
+    t->cfg.hold_seconds = cfg->hold_seconds;      // flood_hold_time, :2225
+    return PPE_OK;
+}
+
+int ppe_portscan_age(ppe_portscan_t *t, uint64_t now_cycles, uint64_t *freed) {
+    if (!t) return PPE_EINVAL;
+    PSCHK(t, hipSetDevice(t->ctx->device));
+    PSCHK(t, hipDeviceSynchronize());
+    unsigned long long d0 = 0, d1 = 0;
+    PSCHK(t, hipMemcpy(&d0, t->ctl + PPE_PSC_DEL, 8, hipMemcpyDeviceToHost));
+    const int rc = ps_rebuild(t, 1, now_cycles);
+    if (rc != PPE_OK) return rc;
+    PSCHK(t, hipMemcpy(&d1, t->ctl + PPE_PSC_DEL, 8, hipMemcpyDeviceToHost));
+    if (freed) *freed = d1 - d0;
+    return PPE_OK;
+}
+
+int ppe_portscan_info(ppe_portscan_t *t, ppe_portscan_info_t *info) {
+    if (!t || !info) return PPE_EINVAL;
+    PSCHK(t, hipSetDevice(t->ctx->device));
+    PSCHK(t, hipDeviceSynchronize());
+    unsigned long long h[PPE_PSC_WORDS];
+    PSCHK(t, hipMemcpy(h, t->ctl, sizeof h, hipMemcpyDeviceToHost));
+    std::memset(info, 0, sizeof *info);
+    info->live = h[PPE_PSC_LIVE];
+    info->new_pcb = h[PPE_PSC_NEW];
+    info->del_pcb = h[PPE_PSC_DEL];
+    info->ok = h[PPE_PSC_OK];
+    info->nomem = h[PPE_PSC_NOMEM];
+    info->detected = h[PPE_PSC_DETECTED];
+    info->hold = h[PPE_PSC_HOLD];
+    info->drop = h[PPE_PSC_DROP];
+    info->cfg = t->cfg;
+    info->slots = t->nslots;
+    info->rebuilds = t->rebuilds;
+    return PPE_OK;
+}
+
+int ppe_portscan_dump(ppe_portscan_t *t, ppe_portscan_entry_t *entries, uint32_t max, uint32_t *n) {
+    if (!t || !n || (max && !entries)) return PPE_EINVAL;
+    PSCHK(t, hipSetDevice(t->ctx->device));
+    PSCHK(t, hipDeviceSynchronize());
+    std::vector<unsigned long long> k(t->nslots), r((size_t)t->nslots * PPE_PS_REC_WORDS);
+    PSCHK(t, hipMemcpy(k.data(), t->keys, k.size() * 8u, hipMemcpyDeviceToHost));
+    PSCHK(t, hipMemcpy(r.data(), t->recs, r.size() * 8u, hipMemcpyDeviceToHost));
+    uint32_t cnt = 0;
+    for (uint32_t s = 0; s < t->nslots; ++s) {
+        const unsigned long long *q = &r[(size_t)s * PPE_PS_REC_WORDS];
+        if (k[s] == 0 || !((uint32_t)q[4] & PPE_PS_LIVE)) continue;
+        if (cnt < max) {
+            ppe_portscan_entry_t &e = entries[cnt];
+            e.sip = (uint32_t)k[s];
+            e.last_dport = (uint32_t)q[4] & 0xffffu;
+            e.exception = (uint32_t)q[3];
+            e.last_exception = (uint32_t)(q[3] >> 32);
+            e.last_cycle = q[0];
+            e.cycle = q[1];
+            e.hold = q[2];
+        }
+        ++cnt;
+    }
+    *n = cnt;
+    return PPE_OK;
+}
+
+const char *ppe_portscan_last_error(ppe_portscan_t *t) { return t ? t->err : "null port-scan table"; }
 
 int ppe_timing_enable(ppe_ctx_t *c, int on) {
     if (!c) return PPE_EINVAL;
@@ -1349,6 +1691,9 @@ int ppe_classify_flow(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *o
     if (!out->verdict) return fail(c, PPE_EINVAL, "ppe_classify_flow needs the verdict output");
     // later packets of a tracked flow need the TCP session state machine (stream-tcp.c:3005-3140): not built
     if (c->stcp.track) return fail(c, PPE_ENOTSUP, "ppe_classify_flow with stream tracking on is not supported");
+    // PortScan_Detect runs on flow misses only (flow.c:196-215), and whether a packet misses depends on the verdicts
+    // of the packets before it: not built
+    if (c->ps) return fail(c, PPE_ENOTSUP, "ppe_classify_flow with a port-scan table attached is not supported");
     int rc = check_batch(c, in, cfg);
     if (rc != PPE_OK || in->n == 0) return rc;
     FlowTable &t = *c->flow;

@@ -26,6 +26,9 @@ struct ppe_bdesc {
 };
 #define PPE_BD_PART8 1u
 #define PPE_BD_PACKED 2u
+/* port-scan launches (ppe_kargs.psmask): flags >> PPE_BD_PSOFF_SHIFT = the word offset of the batch's drop mask (one
+ * 64-bit word per tile) in ppe_kargs.psmask; the descriptor has no spare pointer and keeps its 96 bytes */
+#define PPE_BD_PSOFF_SHIFT 2u
 
 /* Device flow table (ppe_classify_flow; ppe_kernels.hip "flow table").  Open addressing over groups of
  * PPE_FLOW_GROUP slots, linear probing from group flow_hash & gmask; a key lies before the first EMPTY slot of its
@@ -177,8 +180,61 @@ struct ppe_kargs {
        done_target writes done_seq to *done_host (pinned host memory).  done_cnt NULL: not tracked */
     unsigned long long *done_cnt, *done_host;
     unsigned long long done_target, done_seq;
-    struct ppe_flowdev flow;    /* flow-table launches (ppe_classify_flow, one batch) */
+    /* flow-table launches (ppe_classify_flow, one batch): `flow`.  Stateless launches of a context with a port-scan table
+       attached and enabled (the PSC kernels, csrc/ppe_kernels_portscan.hip): `psmask`, the drop masks the pre-pass wrote,
+       one 64-bit word per tile, batch b's at word ppe_bdesc.flags >> PPE_BD_PSOFF_SHIFT; NULL: the kernels without the
+       detector.  The two never meet, so they share the bytes: the argument block keeps its size and every offset */
+    union {
+        struct ppe_flowdev flow;
+        const unsigned long long *psmask;
+    };
 };
+
+/* ---- port-scan detector (csrc/ppe_portscan.hip; dataplane/src/attack/dp_portscan.c) ----
+ * Table: open addressing, linear probing from hash(sip); keys[s] = 0 (empty) or 1 << 32 | sip, never removed between
+ * rebuilds (aging and slot reclamation rebuild the table); recs[s] = PPE_PS_REC_WORDS u64:
+ *   [0] last_cycle [1] cycle [2] portscan_hold_time [3] exception | last_exception << 32
+ *   [4] last_dport | PPE_PS_LIVE | PPE_PS_SERIAL | firstinv << 32
+ * A key without PPE_PS_LIVE holds no record (a source refused with NOMEM keeps its slot until the next rebuild).
+ * firstinv (batch scratch) = max over the batch's packets of a record-less source of ~index: its first appearance. */
+#define PPE_PS_REC_WORDS 5u
+#define PPE_PS_LIVE 0x10000u
+#define PPE_PS_SERIAL 0x20000u   /* batch scratch: the source's packets go through the wave walker */
+#define PPE_PS_NOSLOT 0xffffffffu
+enum { PPE_PS_OK = 0, PPE_PS_NOMEM = 1, PPE_PS_DETECTED = 2, PPE_PS_HOLD = 3, PPE_PS_INELIGIBLE = 0xff };
+enum { PPE_PSC_LIVE = 0, PPE_PSC_NEW, PPE_PSC_DEL, PPE_PSC_OK, PPE_PSC_NOMEM, PPE_PSC_DETECTED, PPE_PSC_HOLD,
+       PPE_PSC_DROP, PPE_PSC_OCC /* keys in use */, PPE_PSC_WORK /* batch: sources queued for the walker */,
+       PPE_PSC_FREE /* batch: capacity - live as the batch started */, PPE_PSC_WORDS = 16 };
+#define PPE_PS_SORT_BLOCK 2048u   /* keys one workgroup sorts in LDS */
+struct ppe_ps_kargs {
+    unsigned long long *keys, *recs, *ctl;
+    uint32_t smask;               /* slots - 1 */
+    uint32_t capacity;
+    /* the batch */
+    const uint8_t *hdr;
+    const uint32_t *len;
+    const uint64_t *ts;
+    uint32_t n, stride, syn_check, npad;   /* npad: sort length, a power of two >= max(n, PPE_PS_SORT_BLOCK) */
+    uint64_t ts_default;          /* cfg->now_seconds: mbuf->timestamp without batch.ts */
+    uint64_t now_cycles, now_seconds, rate;
+    uint32_t freq, hold_seconds, action, sort_k, sort_j, pad;
+    /* batch scratch */
+    uint32_t *slot_of;            /* [n] the packet's slot or PPE_PS_NOSLOT */
+    uint32_t *dport;              /* [n] */
+    uint64_t *pts;                /* [n] mbuf->timestamp */
+    unsigned long long *skey;     /* [npad] slot << 32 | index of the packets with a record, ~0 the rest; sorted */
+    uint8_t *res;                 /* [n] PPE_PS_* */
+    unsigned long long *cmask;    /* [tiles] packets that are their new source's first appearance */
+    uint32_t *cbase;              /* [tiles] their count, then its exclusive prefix */
+    uint32_t *work;               /* [n] sorted positions of the walker's sources */
+    unsigned long long *mask;     /* [tiles] out: the batch's drop mask */
+    /* rebuild */
+    unsigned long long *dkeys, *drecs;
+    uint32_t dmask, age;
+};
+enum { PPE_PS_K_FIND = 0, PPE_PS_K_CREATORS, PPE_PS_K_SCAN, PPE_PS_K_GRANT, PPE_PS_K_KEYS, PPE_PS_K_SORT_LDS,
+       PPE_PS_K_SORT_MERGE_LDS, PPE_PS_K_SORT_GLOBAL, PPE_PS_K_HEADS, PPE_PS_K_MEMBERS, PPE_PS_K_WALK, PPE_PS_K_MASK,
+       PPE_PS_K_REBUILD };
 
 /* flow-hash steering across GPUs (ppe_steer_partition / ppe_gather_rows / ppe_scatter_rows) */
 #define PPE_STEER_MAX_WORLD 16
@@ -270,6 +326,11 @@ int ppe_plan_image(const uint32_t *words, uint32_t n_words, const ppe_tuning_t *
 void ppe_plan_apply(struct ppe_kargs *a, const struct ppe_plan *p);
 /* batch groups (ppe_kargs.max_groups) of a launch over nbatch batches, at most max_groups */
 uint32_t ppe_pick_groups(uint32_t nbatch, uint32_t max_groups);
+/* 1: the launch takes the kernels with the port-scan drop mask (PSC): a stateless launch of a context with a table
+ * attached whose detector is enabled (portscan_able == 1, dp_portscan.c:238) */
+uint32_t ppe_pick_portscan(int flow, int attached, uint32_t able);
+/* one kernel of the port-scan pre-pass (csrc/ppe_portscan.hip), grid sized from the arguments.  Returns hipError_t */
+int ppe_launch_portscan(int kind, const struct ppe_ps_kargs *a, void *stream);
 
 /* Launch the classify kernel. grid = workgroups (persistent). Returns hipError_t.  mode: IMG_*, pipe: PF_* */
 int ppe_launch_classify(const struct ppe_kargs *a, uint32_t grid, int mode, int pipe, int block, int flow,

@@ -14,6 +14,9 @@
  *      counter slot — no contended global atomics).
  *   4b. with StreamTcp tracking on (ppe_stream_tcp_set; the STM instantiations, csrc/ppe_kernels_stream.hip): the
  *      first-packet verdict of StreamTcpPacketStateNone for the TCP packets the ACL forwarded, and its counters;
+ *   4c. with a port-scan table attached and enabled (ppe_portscan_attach; the PSC instantiations,
+ *      csrc/ppe_kernels_portscan*.hip): the lanes in the tile's drop mask, which the pre-pass (csrc/ppe_portscan.hip)
+ *      wrote, become PPE_ST_PORTSCAN_DROP ahead of step 5;
  * No MFMA: integer bitfield / compare work bound by HBM bandwidth and VALU issue.
  *
  * LDS layout of a workgroup (dynamic shared memory, nothing static):
@@ -143,7 +146,8 @@ __device__ __forceinline__ uint32_t reason_counter(uint32_t st) {
         ((uint64_t)PPE_C_WINDOW_PUNT << 30) | ((uint64_t)PPE_C_FLOW_NODE_NOMEM << 35) |
         ((uint64_t)PPE_C_ACL_FW << 40) | ((uint64_t)PPE_C_ACL_FW << 45) | ((uint64_t)PPE_C_ACL_FW << 50) |
         ((uint64_t)PPE_C_ACL_FW << 55);
-    static_assert(PPE_ST__COUNT == 24, "reason table covers statuses 0..23");
+    // (status 24, PPE_ST_PORTSCAN_DROP, has no reason counter of its own: bin_counters<true> takes it before this table)
+    static_assert(PPE_ST__COUNT == 24 && PPE_ST__END == 25, "reason table covers statuses 0..23");
     const bool lo = st < 12u;
     return (uint32_t)(((lo ? K0 : K1) >> (5u * (lo ? st : st - 12u))) & 31u);
 }
@@ -269,9 +273,16 @@ struct MacValues {
 //   FLOW_PROC_OK / _FAIL by the flow engine's outcome; OUT_FW / OUT_DROP / OUT_PUNT by the action.
 #define PPE_NBINS 256u
 static_assert(PPE_F_VLAN == 1u && PPE_F_L4 == 2u && PPE_F_TCP == 4u, "bin key layout");
+// PSC (kernels with the port-scan drop mask): status 24 is PortScan_Detect's drop, before the ACL (flow.c:216-230): the
+// RX_OK chain of a packet that reached the flow engine, STAT_FLOW_PROC_FAIL (:281-282) and OUT_DROP; no ACL_*, no
+// FLOW_PROC_OK (attstat.portscan_drop itself is the table's counter, ppe_portscan_info_t.drop)
+template <bool PSC = false>
 __device__ __forceinline__ uint32_t bin_counters(uint32_t key, uint64_t act_table) {
     const uint32_t st = key & 31u;
     const bool vl = (key >> 5) & 1u, l4 = (key >> 6) & 1u, tcp = (key >> 7) & 1u;
+    if (PSC && st == PPE_ST_PORTSCAN_DROP)
+        return CB(PPE_C_PKTS) | CB(PPE_C_L2_RX_OK) | (vl ? CB(PPE_C_VLAN_RX_OK) : 0u) | CB(PPE_C_IPV4_RX_OK) |
+               (tcp ? CB(PPE_C_TCP_RX_OK) : CB(PPE_C_UDP_RX_OK)) | CB(PPE_C_FLOW_PROC_FAIL) | CB(PPE_C_OUT_DROP);
     uint32_t cb = CB(PPE_C_PKTS) | CB(reason_counter(st));
     if (st != PPE_ST_L2_HEADER_ERR && st != PPE_ST_L2_UNSUPPORT) cb |= CB(PPE_C_L2_RX_OK);
     if (vl && st != PPE_ST_VLAN_UNSUPPORT) cb |= CB(PPE_C_VLAN_RX_OK);
@@ -316,8 +327,13 @@ __device__ __forceinline__ __attribute__((unused)) uint32_t stream_tcp_none(uint
     s = (sf & 0x04u) ? (uint32_t)PPE_ST_STREAM_RST_NO_SESSION : s;                                  // RST, :243-248
     return s;
 }
-// the bins (status 24..27, flags 0: no such status) that hold a workgroup's StreamTcp count-first counters
+// the bins (keys 24..27 = status 24..27 with flags 0) that hold a workgroup's StreamTcp count-first counters.  Status
+// 24 exists since the port-scan detector (PPE_ST_PORTSCAN_DROP), but only for packets that reached PortScan_Detect:
+// those carry PPE_F_L4, so their bin key is 24 | 64 (| 32 | 128), never 24..27
 #define PPE_STREAM_BIN0 24u
+#define PPE_STREAM_ST_END 24u  // statuses [PPE_ST_STREAM_RST_NO_SESSION, this) are StreamTcp's drop reasons
+static_assert(PPE_ST_PORTSCAN_DROP == PPE_STREAM_BIN0 && (PPE_F_L4 << 5) > PPE_STREAM_BIN0 + 3u,
+              "a port-scan drop's bin (status 24, PPE_F_L4 set: key >= 64) stays clear of the stream bins 24..27");
 
 // Decode of one packet, straight-line: every check of the reference is evaluated, then the terminal status is
 // chosen by applying the checks in REVERSE order of the reference's control flow, so the first failing check
@@ -1014,10 +1030,13 @@ __device__ __forceinline__ void stage_image(const uint32_t *img, uint32_t *lds, 
 
 // action of each terminal status, 2 bits per status: FW for ACL_FW, PUNT for fragments / short windows, the
 // configured action for unsupported protocols (Decode_unsupport_proto_handle, decode.c:31-45), else DROP
+// (NST: statuses in the table; the kernels without the port-scan mask keep the 24-entry constant)
+template <uint32_t NST = PPE_ST__COUNT>
 __device__ __forceinline__ uint64_t make_act_table(uint32_t unsup_fw) {
+    static_assert(NST <= PPE_ST__END && 2u * NST <= 64u, "2 bits per status");
     uint64_t t = 0;
 #pragma unroll
-    for (uint32_t st = 0; st < PPE_ST__COUNT; ++st) {
+    for (uint32_t st = 0; st < NST; ++st) {
         const uint64_t ac = st == PPE_ST_ACL_FW ? PPE_ACT_FW
                           : (st == PPE_ST_L2_UNSUPPORT || st == PPE_ST_VLAN_UNSUPPORT || st == PPE_ST_IPV4_UNSUPPORT)
                               ? (unsup_fw ? PPE_ACT_FW : PPE_ACT_DROP)
@@ -1300,7 +1319,9 @@ __device__ __forceinline__ uint32_t flow_find_claim(const ppe_flowdev &f, const 
 // STM: StreamTcp's first-packet verdict (ppe_stream_tcp_set tracking on; stateless kernels only).  A template
 // parameter, not a run-time branch: the 64-VGPR kernels have no register to spare (as a uniform branch the check
 // cost C1's kernel 2 spilled VGPRs with tracking off), so with tracking off the kernels contain none of it.
-template <int MODE, int PF, int BLOCK, bool FLOW, bool PART = false, bool STM = false>
+// PSC: the port-scan detector's drop mask (a table with able = 1 attached, ppe_portscan_attach; stateless kernels only;
+// csrc/ppe_kernels_portscan.hip), a template parameter for the same reason; combines with STM.
+template <int MODE, int PF, int BLOCK, bool FLOW, bool PART = false, bool STM = false, bool PSC = false>
 __global__ __launch_bounds__(BLOCK, (PF == PF_MULTI && !FLOW) ? PPE_MT_WAVES
                                     : FLOW                                       ? PPE_FLOW_WAVES
                                     : (PF == PF_CUT && MODE == IMG_LDS)          ? PPE_CUT_LDS_WAVES
@@ -1316,6 +1337,7 @@ void ppe_classify_kernel(ppe_kargs a) {
     constexpr bool CUT = PF == PF_CUT && !FLOW;
     constexpr bool KEYS = MT == 1 && !CUT;  // node walks: per-wave key slots in LDS
     static_assert(!(STM && FLOW), "stream tracking: stateless kernels only");
+    static_assert(!(PSC && FLOW), "port-scan mask: stateless kernels only");
     const uint32_t stm = STM ? a.stream : 0u;
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     using L = Lds<BLOCK, KEYS, FLOW ? 4u * PPE_UPD_OWNERS * (1u + (PPE_UPD_LDS ? PPE_UPD_CAP : 0u)) : 0u>;
@@ -1383,7 +1405,7 @@ void ppe_classify_kernel(ppe_kargs a) {
                         a.cut, a.cut_slc, a.cut_gbase, a.cut_fp, a.cut_ent, a.cut_epl, a.cut_div, a.cut_idrel,
                         a.cut_gbase_lds, a.cut_fp_lds, a.cut_ent_lds};
 
-    const uint64_t act_table = make_act_table(a.unsup_fw);
+    const uint64_t act_table = make_act_table<PSC ? PPE_ST__END : PPE_ST__COUNT>(a.unsup_fw);
     // (this batch's creator counter was zeroed by the previous batch's finalize launch)
     if (FLOW && blockIdx.x == 0 && tid == 0) {
         // the table state after the previous batches, for the host's bounds (zero-copy, no stream stall); LIVE is
@@ -1402,6 +1424,17 @@ void ppe_classify_kernel(ppe_kargs a) {
 
     // after the ACL: verdict / hash / hit stores, FLOW pending records, compaction, counters
     // (sfw >> PPE_SF_SHIFT = the packet's StreamTcp flag bits, read only with tracking on)
+    // PSC, ahead of finish(): PortScan_Detect said NOMEM, DETECTED or HOLD with action drop (the pre-pass's mask, one
+    // word per tile): return NULL before the ACL (flow.c:216-230), whatever the walk found: status 24, no ACL hit, no
+    // PPE_F_ACL; flow hash, tuple and the other flags stay.  finish() then sees no ACL_FW: not a packet for StreamTcp
+    auto portscan_drop = [&](uint32_t tile, bool valid, Dec &k, int32_t &hit) {
+        const unsigned long long pm = a.psmask[(B.flags >> PPE_BD_PSOFF_SHIFT) + tile];
+        if (valid && ((pm >> lane) & 1ull)) {
+            k.st = PPE_ST_PORTSCAN_DROP;
+            hit = -1;
+            k.flags &= ~(uint32_t)PPE_F_ACL;
+        }
+    };
     auto finish = [&](uint32_t tile, uint32_t p, bool valid, const Dec &k, uint32_t fh, int32_t hit, bool pend,
                       uint32_t sfw) {
         uint32_t st = k.st;
@@ -1533,6 +1566,7 @@ void ppe_classify_kernel(ppe_kargs a) {
             k.st = drop ? (uint32_t)PPE_ST_ACL_DROP : (uint32_t)PPE_ST_ACL_FW;
             k.flags |= PPE_F_ACL;
         }
+        if constexpr (PSC) portscan_drop(tile, valid, k, hit);
         finish(tile, p, valid, k, fh, hit, pend, k.flags);
     };
 
@@ -1583,7 +1617,13 @@ void ppe_classify_kernel(ppe_kargs a) {
             k.st = drop ? (uint32_t)PPE_ST_ACL_DROP : (uint32_t)PPE_ST_ACL_FW;
             k.flags |= PPE_F_ACL;
         }
-        finish(tile, p, p < B.n, k, fh, need ? hit : -1, false, key[3] >> 8);
+        if constexpr (PSC) {
+            int32_t h = need ? hit : -1;
+            portscan_drop(tile, p < B.n, k, h);
+            finish(tile, p, p < B.n, k, fh, h, false, key[3] >> 8);
+        } else {
+            finish(tile, p, p < B.n, k, fh, need ? hit : -1, false, key[3] >> 8);
+        }
     };
     // a leaf's rule check (non-compact images: leaf lists / residual fields, rare)
     auto mt_leaf = [&](uint32_t tile, const uint32_t (&key)[4], const uint4 &nd, int32_t &hit, bool &drop) {
@@ -1749,19 +1789,20 @@ void ppe_classify_kernel(ppe_kargs a) {
     for (uint32_t b = tid; b < PPE_NBINS; b += BLOCK) {  // expand the bins into counter increments
         const uint32_t c = bins[b];
         if (c) {
-            if (STM && (b & 31u) >= PPE_ST_STREAM_RST_NO_SESSION) {
+            if (STM && (b & 31u) >= PPE_ST_STREAM_RST_NO_SESSION &&
+                !(PSC && b >= 32u && (b & 31u) == PPE_ST_PORTSCAN_DROP)) {
                 // StreamTcp tracking: this workgroup's counts into its own stream counter slot (uncontended), one add
                 // per non-empty bin: the count-first accumulators, and each drop's reason (its status bins)
                 const uint32_t st = b & 31u;
                 const uint32_t sc =
-                    st < PPE_ST__COUNT ? (uint32_t)PPE_SC_RST_BUT_NO_SESSION + st - PPE_ST_STREAM_RST_NO_SESSION
+                    st < PPE_STREAM_ST_END ? (uint32_t)PPE_SC_RST_BUT_NO_SESSION + st - PPE_ST_STREAM_RST_NO_SESSION
                     : (b & 3u) == 3u   ? (uint32_t)PPE_SC_PKT_BROKEN_ACK  // (bins PPE_STREAM_BIN0 + 0..3)
                                        : (uint32_t)PPE_SC_SYN_ACK_COUNT + (b & 3u);
                 __hip_atomic_fetch_add(&a.sslots[(size_t)blockIdx.x * PPE_SSLOT_WORDS + sc], (unsigned long long)c,
                                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (st >= PPE_ST__COUNT) continue;
+                if (st >= PPE_STREAM_ST_END) continue;
             }
-            for (uint32_t cb = bin_counters(b, act_table); cb; cb &= cb - 1u) atomicAdd(&lcnt[__builtin_ctz(cb)], c);
+            for (uint32_t cb = bin_counters<PSC>(b, act_table); cb; cb &= cb - 1u) atomicAdd(&lcnt[__builtin_ctz(cb)], c);
         }
     }
     if (FLOW && blockIdx.x < a.flow.upd_wgs) {  // this workgroup's row of bucket counts, for the update kernel
@@ -2392,7 +2433,40 @@ __global__ __launch_bounds__(PPE_BLOCK) void ppe_acl_tuple_kernel(ppe_tuple_karg
         PPE_DISPATCH_P(FN, IMG_GLOBAL, __VA_ARGS__);                 \
     } while (0)
 
-#if defined(PPE_TU_STREAM)
+#if defined(PPE_TU_PORTSCAN_PRE)
+// csrc/ppe_portscan.hip: this file for its decode(); the pre-pass kernels follow the include, nothing is exported here
+#elif defined(PPE_TU_PORTSCAN)
+// csrc/ppe_kernels_portscan.hip / ppe_kernels_portscan_stream.hip: this file again, exporting only the stateless
+// kernels with the port-scan drop mask (PSC), without (PPE_TU_PORTSCAN 1) or with (2) StreamTcp's verdict
+constexpr bool kPscStm = PPE_TU_PORTSCAN == 2;
+template <int M, int P, int B>
+static int launch_psc_t(const ppe_kargs *a, uint32_t grid, size_t shmem, hipStream_t s, hipEvent_t e0,
+                        hipEvent_t e1) {
+    if constexpr (P != PF_NONE) {  // (the throughput-layout variants exist for the same fetch modes as without PSC)
+        if (a->part_layout)
+            hipExtLaunchKernelGGL((ppe_classify_kernel<M, P, B, false, true, kPscStm, true>), dim3(grid), dim3(B),
+                                  shmem, s, e0, e1, 0, *a);
+        else
+            hipExtLaunchKernelGGL((ppe_classify_kernel<M, P, B, false, false, kPscStm, true>), dim3(grid), dim3(B),
+                                  shmem, s, e0, e1, 0, *a);
+    } else {
+        hipExtLaunchKernelGGL((ppe_classify_kernel<M, P, B, false, false, kPscStm, true>), dim3(grid), dim3(B), shmem,
+                              s, e0, e1, 0, *a);
+    }
+    return (int)hipGetLastError();
+}
+#if PPE_TU_PORTSCAN == 2
+extern "C" int ppe_launch_classify_portscan_stream(
+#else
+extern "C" int ppe_launch_classify_portscan(
+#endif
+    const ppe_kargs *a, uint32_t grid, size_t shmem, int mode, int pipe, int block, void *stream, void *ev_start,
+    void *ev_stop) {
+    const hipStream_t s = (hipStream_t)stream;
+    const hipEvent_t e0 = (hipEvent_t)ev_start, e1 = (hipEvent_t)ev_stop;
+    PPE_DISPATCH(launch_psc_t, a, grid, shmem, s, e0, e1);
+}
+#elif defined(PPE_TU_STREAM)
 // csrc/ppe_kernels_stream.hip: this file again, exporting only the stateless kernels with StreamTcp's verdict (STM)
 template <int M, int P, int B>
 static int launch_stream_t(const ppe_kargs *a, uint32_t grid, size_t shmem, hipStream_t s, hipEvent_t e0,
@@ -2457,6 +2531,10 @@ extern "C" int ppe_launch_classify_hoist_lds(const ppe_kargs *a, uint32_t grid, 
 extern "C" int ppe_occupancy_hoist_lds(size_t shmem, int block);
 extern "C" int ppe_launch_classify_stream(const ppe_kargs *a, uint32_t grid, size_t shmem, int mode, int pipe,
                                           int block, void *stream, void *ev_start, void *ev_stop);
+extern "C" int ppe_launch_classify_portscan(const ppe_kargs *a, uint32_t grid, size_t shmem, int mode, int pipe,
+                                            int block, void *stream, void *ev_start, void *ev_stop);
+extern "C" int ppe_launch_classify_portscan_stream(const ppe_kargs *a, uint32_t grid, size_t shmem, int mode, int pipe,
+                                                   int block, void *stream, void *ev_start, void *ev_stop);
 
 template <int M, int P, int B>
 static int launch_t(const ppe_kargs *a, uint32_t grid, size_t shmem, hipStream_t s, hipEvent_t e0, hipEvent_t e1,
@@ -2506,6 +2584,11 @@ extern "C" int ppe_launch_classify(const ppe_kargs *a, uint32_t grid, int mode, 
     const size_t shmem = classify_shmem(a->stage_words, mode, pipe, block, flow != 0);
     // StreamTcp tracking on: the same kernel with the verdict compiled in (same launch bounds and LDS, so the same
     // occupancy and grid), from its own translation unit
+    // a port-scan table attached and enabled: the kernels that read the pre-pass's drop mask, with or without StreamTcp
+    // (same launch bounds and LDS again)
+    if (a->psmask && !flow)
+        return (a->stream ? ppe_launch_classify_portscan_stream : ppe_launch_classify_portscan)(
+            a, grid, shmem, mode, pipe, block, stream, ev_start, ev_stop);
     if (a->stream && !flow)
         return ppe_launch_classify_stream(a, grid, shmem, mode, pipe, block, stream, ev_start, ev_stop);
     hipStream_t s = (hipStream_t)stream;

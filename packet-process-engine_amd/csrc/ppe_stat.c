@@ -24,6 +24,7 @@
 /* reassembly-table sources (ppe_defrag_info_t), printed 0 without one */
 #define DF(st) (1000 + (st))   /* fragments with Defrag outcome st */
 #define DF_TEARDROP 2000       /* overlaps, while the teardrop monitor is enabled */
+#define PS_DROP 3000           /* attstat.portscan_drop of a port-scan table (ppe_portscan_info_t), printed 0 without one */
 
 typedef struct {
     const char *name;  /* printed as "<name>: %ld" */
@@ -75,7 +76,7 @@ static const stat_line_t k_tx[] = {{"port_err", NONE}, {"hw_send_err", NONE}, {"
                                    {"sw_send_err", NONE}, {"send_over", NONE}};
 static const stat_line_t k_att[] = {{"land_drop", NONE}, {"teardrop", DF_TEARDROP}, {"pingdeath", NONE},
                                     {"ping flood drop", NONE}, {"udp flood drop", NONE}, {"syn flood drop", NONE},
-                                    {"syncount", NONE}, {"portscan_drop", NONE}};
+                                    {"syncount", NONE}, {"portscan_drop", PS_DROP}};
 
 #define SEC(t, a, b) {t, a, (int)(sizeof a / sizeof a[0]), b}
 static const stat_section_t k_sections[] = {
@@ -100,8 +101,10 @@ static void put(out_t *o, const char *fmt, ...) {
     if (k > 0) o->len += (size_t)k;
 }
 
-static long line_value(const ppe_counters_t *c, const ppe_defrag_info_t *df, int teardrop_monitor, int ci) {
+static long line_value(const ppe_counters_t *c, const ppe_defrag_info_t *df, int teardrop_monitor,
+                       const ppe_portscan_info_t *ps, int ci) {
     if (ci == NONE) return 0L;
+    if (ci == PS_DROP) return ps ? (long)ps->drop : 0L;
     if (ci == DF_TEARDROP) return df && teardrop_monitor ? (long)df->teardrop : 0L;
     if (ci >= 1000) return df ? (long)df->st[ci - 1000] : 0L;
     return (long)c->c[ci];
@@ -113,6 +116,11 @@ int ppe_format_pkt_stat(const ppe_counters_t *c, char *buf, size_t cap) {
 
 int ppe_format_pkt_stat_ex(const ppe_counters_t *c, const ppe_defrag_info_t *df, int teardrop_monitor, char *buf,
                            size_t cap) {
+    return ppe_format_pkt_stat_ps(c, df, teardrop_monitor, NULL, buf, cap);
+}
+
+int ppe_format_pkt_stat_ps(const ppe_counters_t *c, const ppe_defrag_info_t *df, int teardrop_monitor,
+                           const ppe_portscan_info_t *ps_info, char *buf, size_t cap) {
     if (!c) return PPE_EINVAL;
     out_t o = {buf, buf ? cap : 0, 0};
     if (buf && cap) buf[0] = 0;
@@ -125,11 +133,24 @@ int ppe_format_pkt_stat_ex(const ppe_counters_t *c, const ppe_defrag_info_t *df,
         put(&o, "----------------\n");
         for (int i = 0; i < sec->n; i++) {
             const int ci = sec->lines[i].counter;
-            put(&o, "%s: %ld\n", sec->lines[i].name, line_value(c, df, teardrop_monitor, ci));
+            put(&o, "%s: %ld\n", sec->lines[i].name, line_value(c, df, teardrop_monitor, ps_info, ci));
         }
         put(&o, "----------------\n");
         if (sec->blank_after) put(&o, "\n");
     }
+    return (int)o.len;
+}
+
+/* the port-scan lines of `show fw config` (dp_cmd.c:2578-2590), same format strings */
+int ppe_format_fw_config(const ppe_portscan_cfg_t *cfg, char *buf, size_t cap) {
+    const ppe_portscan_cfg_t ref = {1u, 0u, 50u, 600u, 0u, 0u, 0u, 0u}; /* dp_portscan.c:9-11, dp_attack.c:25 */
+    const ppe_portscan_cfg_t *v = cfg ? cfg : &ref;
+    out_t o = {buf, buf ? cap : 0, 0};
+    if (buf && cap) buf[0] = 0;
+    put(&o, "portscan attack detect stat: %s\n", v->able ? "enable" : "disable");
+    put(&o, "portscan attack detect action: %s\n", v->action ? "fw" : "drop");
+    put(&o, "flood hold time: %d\n", (int)v->hold_seconds);
+    put(&o, "portscan_exception_freq: %d\n", (int)v->exception_freq);
     return (int)o.len;
 }
 

@@ -23,7 +23,10 @@ ST = dict(ACL_FW=0, ACL_DROP=1, L2_HEADER_ERR=2, L2_UNSUPPORT=3, VLAN_HEADER_ERR
           FLOW_TCP_NO_SYN_FIRST=17, WINDOW_PUNT=18, FLOW_NOMEM=19,
           # StreamTcp's first-packet verdict (ppe_stream_tcp_set tracking on)
           STREAM_RST_NO_SESSION=20, STREAM_FIN_NO_SESSION=21, STREAM_MIDSTREAM_ONESIDE_OFF=22,
-          STREAM_MIDSTREAM_OFF=23)
+          STREAM_MIDSTREAM_OFF=23,
+          # PortScan_Detect's drop (a table attached with ppe_portscan_attach)
+          PORTSCAN_DROP=24)
+ST_COUNT, ST_END = 24, 25  # PPE_ST__COUNT (statuses without a port-scan table), PPE_ST__END (all of them)
 ST_NAME = {v: k for k, v in ST.items()}
 # enum ppe_stream_counter (ppe_stream_counters_t.c[])
 STREAM_COUNTERS = ["syn_ack_count", "syn_count", "rst_count", "rst_but_no_session", "fin_but_no_session",
@@ -113,6 +116,32 @@ class StreamCounters(C.Structure):  # ppe_stream_counters_t
 
     def as_dict(self):
         return {name: int(self.c[i]) for i, name in enumerate(STREAM_COUNTERS)}
+
+
+class PortScanCfg(C.Structure):  # ppe_portscan_cfg_t
+    _fields_ = [("able", C.c_uint32), ("action", C.c_uint32), ("exception_freq", C.c_uint32),
+                ("hold_seconds", C.c_uint32), ("capacity", C.c_uint32), ("max_batch", C.c_uint32),
+                ("cycles_per_second", C.c_uint64), ("pad", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
+
+
+class PortScanInfo(C.Structure):  # ppe_portscan_info_t
+    _fields_ = [("live", C.c_uint64), ("new_pcb", C.c_uint64), ("del_pcb", C.c_uint64), ("ok", C.c_uint64),
+                ("nomem", C.c_uint64), ("detected", C.c_uint64), ("hold", C.c_uint64), ("drop", C.c_uint64),
+                ("cfg", PortScanCfg), ("slots", C.c_uint32), ("rebuilds", C.c_uint32)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "cfg"}
+        d["cfg"] = self.cfg.as_dict()
+        return d
+
+
+# ppe_portscan_entry_t (include/ppe_hip.h), 40 bytes
+PORTSCAN_ENTRY_DTYPE = np.dtype([("sip", "<u4"), ("last_dport", "<u4"), ("exception", "<u4"),
+                                 ("last_exception", "<u4"), ("last_cycle", "<u8"), ("cycle", "<u8"), ("hold", "<u8")])
+assert PORTSCAN_ENTRY_DTYPE.itemsize == 40
 
 
 class Tuning(C.Structure):
@@ -246,8 +275,11 @@ EXPORTS = [
     "ppe_defrag_last_error",
     "ppe_stream_tcp_set", "ppe_stream_tcp_get", "ppe_stream_counters_read", "ppe_stream_counters_clear",
     "ppe_format_tcpstream_stat",
+    "ppe_portscan_create", "ppe_portscan_destroy", "ppe_portscan_attach", "ppe_portscan_clock", "ppe_portscan_set",
+    "ppe_portscan_age", "ppe_portscan_info", "ppe_portscan_dump", "ppe_portscan_last_error",
+    "ppe_format_pkt_stat_ps", "ppe_format_fw_config",
     # csrc/ppe_internal.h: the host-only launch planner (internal helpers, not part of the public headers)
-    "ppe_plan_image", "ppe_pick_groups",
+    "ppe_plan_image", "ppe_pick_groups", "ppe_pick_portscan",
     # ppe_acl.h
     "ppe_rule_list_init", "ppe_rule_list_free", "Rule_add", "Rule_del_by_id", "Rule_del_all",
     "Rule_duplicate_check", "Rule_Load_Line", "ppe_rule_load_file", "DP_Acl_Rule_Init", "DP_Acl_Load_Rule",
@@ -351,8 +383,21 @@ def _open(p: Path, mode, strict: bool = True) -> C.CDLL:
         "ppe_stream_counters_clear": ([vp], C.c_int),
         "ppe_format_tcpstream_stat": ([C.POINTER(StreamCounters), C.POINTER(StreamTcpCfg), C.c_char_p, C.c_size_t],
                                       C.c_int),
+        "ppe_portscan_create": ([vp, C.POINTER(PortScanCfg), C.POINTER(vp)], C.c_int),
+        "ppe_portscan_destroy": ([vp], C.c_int),
+        "ppe_portscan_attach": ([vp, vp], C.c_int),
+        "ppe_portscan_clock": ([vp, u64, u64], C.c_int),
+        "ppe_portscan_set": ([vp, C.POINTER(PortScanCfg)], C.c_int),
+        "ppe_portscan_age": ([vp, u64, C.POINTER(u64)], C.c_int),
+        "ppe_portscan_info": ([vp, C.POINTER(PortScanInfo)], C.c_int),
+        "ppe_portscan_dump": ([vp, vp, u32, C.POINTER(u32)], C.c_int),
+        "ppe_portscan_last_error": ([vp], C.c_char_p),
+        "ppe_format_pkt_stat_ps": ([C.POINTER(Counters), C.POINTER(DefragInfo), C.c_int, C.POINTER(PortScanInfo),
+                                    C.c_char_p, C.c_size_t], C.c_int),
+        "ppe_format_fw_config": ([C.POINTER(PortScanCfg), C.c_char_p, C.c_size_t], C.c_int),
         "ppe_plan_image": ([vp, u32, C.POINTER(Tuning), C.c_int, C.POINTER(Plan)], C.c_int),
         "ppe_pick_groups": ([u32, u32], u32),
+        "ppe_pick_portscan": ([C.c_int, C.c_int, u32], u32),
         "ppe_rule_list_init": ([], C.c_int),
         "ppe_rule_list_free": ([], None),
         "Rule_add": ([vp, C.POINTER(u32)], C.c_int),

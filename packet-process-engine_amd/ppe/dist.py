@@ -113,6 +113,10 @@ class DeviceSteerOps:
         self.eng._check(self.eng.lib.ppe_stream_tcp_get(self.eng.ctx, C.byref(cfg)), "ppe_stream_tcp_get")
         return bool(cfg.track)
 
+    def portscan_attached(self) -> bool:
+        """A port-scan table is attached to this engine (Engine.portscan; ppe_classify_flow then returns PPE_ENOTSUP)."""
+        return getattr(self.eng, "portscan_attached", None) is not None
+
     def classify_flow(self, hdr, lens, cfg):
         t = self.torch
         n = lens.numel()
@@ -146,6 +150,9 @@ def steered_classify_flow(ops, dist, hdr, lens, cfg, world: int, rank: int) -> d
     if getattr(ops, "stream_tracking", None) and ops.stream_tracking():
         raise PPEError(f"ppe_classify_flow failed: {abi.PPE_ENOTSUP}: stream tracking is on (ppe_stream_tcp_set); "
                        "the flow-table path does not support it")
+    if getattr(ops, "portscan_attached", None) and ops.portscan_attached():  # the same for an attached port-scan table
+        raise PPEError(f"ppe_classify_flow failed: {abi.PPE_ENOTSUP}: a port-scan table is attached "
+                       "(ppe_portscan_attach); the flow-table path does not support it")
     perm, counts, send_hdr, send_len = steer_prepare(ops, hdr, lens, cfg, world, rank)
     send_counts = counts.to(torch.int64)
     recv_counts = torch.empty_like(send_counts)

@@ -222,6 +222,15 @@ class Engine:
     def clear_stream_counters(self):
         self._check(self.lib.ppe_stream_counters_clear(self.ctx), "ppe_stream_counters_clear")
 
+    # ---- port-scan detector (ppe_portscan_*, dataplane/src/attack/dp_portscan.c) ----
+    def portscan(self, attach: bool = True, **cfg) -> "PortScan":
+        """ppe_portscan_create (cfg: the words of ppe_portscan_cfg_t; none given = the reference's defaults) and, unless
+        attach is false, ppe_portscan_attach: later ppe_classify / ppe_classify_batches launches run the detector."""
+        ps = PortScan(self, **cfg)
+        if attach:
+            ps.attach()
+        return ps
+
     def timing(self, on: bool = True):
         self._check(self.lib.ppe_timing_enable(self.ctx, 1 if on else 0), "ppe_timing_enable")
 
@@ -323,3 +332,75 @@ class Defrag:
         self._check(self.lib.ppe_defrag_info(self.h, C.byref(fi)), "ppe_defrag_info")
         return fi.as_dict()
 
+
+
+class PortScan:
+    """One port-scan table (ppe_portscan_create) on an Engine's GPU: PortScan_Detect on the stateless classify path
+    (dataplane/src/attack/dp_portscan.c).  Every call goes through libppe_hip.so."""
+
+    def __init__(self, engine: Engine, **cfg):
+        self.eng = engine
+        self.lib = engine.lib
+        self.h = C.c_void_p()
+        c = None
+        if cfg:
+            d = dict(able=1, action=0, exception_freq=50, hold_seconds=600, capacity=0, max_batch=0, cycles_per_second=0)
+            unknown = set(cfg) - set(d)
+            if unknown:
+                raise TypeError(f"unknown ppe_portscan_cfg_t words: {sorted(unknown)}")
+            d.update(cfg)
+            c = abi.PortScanCfg(**{k: int(v) for k, v in d.items()})
+        rc = self.lib.ppe_portscan_create(engine.ctx, C.byref(c) if c is not None else None, C.byref(self.h))
+        if rc != 0:
+            raise PPEError(f"ppe_portscan_create failed: {rc}")
+
+    def _check(self, rc, what):
+        if rc != 0:
+            err = self.lib.ppe_portscan_last_error(self.h)
+            raise PPEError(f"{what} failed: {rc}: {err.decode() if err else ''}")
+
+    def attach(self):
+        self.eng._check(self.lib.ppe_portscan_attach(self.eng.ctx, self.h), "ppe_portscan_attach")
+        self.eng.portscan_attached = self
+
+    def detach(self):
+        self.eng._check(self.lib.ppe_portscan_attach(self.eng.ctx, None), "ppe_portscan_attach")
+        self.eng.portscan_attached = None
+
+    def close(self):
+        if self.h:
+            self.lib.ppe_portscan_destroy(self.h)  # (detaches it first)
+            if getattr(self.eng, "portscan_attached", None) is self:
+                self.eng.portscan_attached = None
+            self.h = C.c_void_p()
+
+    def clock(self, now_cycles: int, now_seconds: int):
+        """cvmx_get_cycle() and OCT_TIME_SECONDS_SINCE1970 for the batches enqueued from now on."""
+        self._check(self.lib.ppe_portscan_clock(self.h, int(now_cycles), int(now_seconds)), "ppe_portscan_clock")
+
+    def set(self, **kw) -> dict:
+        """able / action / exception_freq / hold_seconds, live; the words not given keep their values."""
+        cur = self.info()["cfg"]
+        cur.update({k: int(v) for k, v in kw.items()})
+        c = abi.PortScanCfg(**cur)
+        self._check(self.lib.ppe_portscan_set(self.h, C.byref(c)), "ppe_portscan_set")
+        return self.info()["cfg"]
+
+    def age(self, now_cycles: int) -> int:
+        """PortScan_timeout: returns the records freed."""
+        freed = C.c_uint64(0)
+        self._check(self.lib.ppe_portscan_age(self.h, int(now_cycles), C.byref(freed)), "ppe_portscan_age")
+        return freed.value
+
+    def info(self) -> dict:
+        i = abi.PortScanInfo()
+        self._check(self.lib.ppe_portscan_info(self.h, C.byref(i)), "ppe_portscan_info")
+        return i.as_dict()
+
+    def dump(self) -> np.ndarray:
+        n = C.c_uint32(0)
+        self._check(self.lib.ppe_portscan_dump(self.h, None, 0, C.byref(n)), "ppe_portscan_dump")
+        ent = np.zeros(n.value, abi.PORTSCAN_ENTRY_DTYPE)
+        if n.value:
+            self._check(self.lib.ppe_portscan_dump(self.h, ent.ctypes.data, n.value, C.byref(n)), "ppe_portscan_dump")
+        return ent
