@@ -241,12 +241,16 @@ __device__ __forceinline__ uint32_t tcp_ws_offset(const uint8_t *row, uint32_t o
 
 // Where a residual MAC rule gets the packet's MACs: re-read from the header window (classify kernel: rare path, keeps
 // the MACs out of registers during the walk) or given by value (tuple kernel).
+// A lane past the end of its batch carries the last packet's window (the tile loads clamp the index), so p may lie
+// up to a tile round past n - 1: every rare-path read clamps it the same way, inside the rare branch itself (nothing
+// on the hot path), and stays inside the caller's buffers.
 struct MacFromWindow {
     const uint8_t *hdr;
-    uint32_t p, stride;
+    uint32_t p, n, stride;
+    __device__ __forceinline__ uint32_t row(uint32_t i) const { return min(i, n - 1u); }  // index of per-packet arrays
     __device__ __forceinline__ void get(uint32_t &dlo, uint32_t &dhi, uint32_t &slo, uint32_t &shi) const {
         uint32_t w0, w1, w2;  // dmac = bytes 0-5, smac = bytes 6-11 (EthernetHdr, decode-ethernet.h:23-27)
-        ld_mac_sync(hdr + (size_t)p * stride, w0, w1, w2);
+        ld_mac_sync(hdr + (size_t)row(p) * stride, w0, w1, w2);
         dlo = w0;
         dhi = w1 & 0xffffu;
         slo = (w1 >> 16) | (w2 << 16);
@@ -255,6 +259,7 @@ struct MacFromWindow {
 };
 struct MacValues {
     uint32_t dlo, dhi, slo, shi;
+    __device__ __forceinline__ uint32_t row(uint32_t i) const { return i; }
     __device__ __forceinline__ void get(uint32_t &a, uint32_t &b, uint32_t &c, uint32_t &d) const {
         a = dlo;
         b = dhi;
@@ -338,12 +343,13 @@ static_assert(PPE_ST_PORTSCAN_DROP == PPE_STREAM_BIN0 && (PPE_F_L4 << 5) > PPE_S
 // Decode of one packet, straight-line: every check of the reference is evaluated, then the terminal status is
 // chosen by applying the checks in REVERSE order of the reference's control flow, so the first failing check
 // (the one the reference returns on) wins.  w[0..12] = first 52 bytes (little-endian dwords); hdr / p = the packet's
-// window in global memory (read only for L4 headers behind IPv4 options).
+// window in global memory (read only for L4 headers behind IPv4 options, at index min(p, n - 1): a lane past the end
+// of the n-packet batch decodes the last packet's window, and must read that packet's row).
 // TUP (kernels that may write the tuple output): a fragment's sport / dport / paylen carry what DecodeIPV4 records
 // for Defrag instead (decode-ipv4.c:106-109): ip_id, the fragment offset in bytes and frag_len (ppe_hip.h tuple).
 template <bool TUP = true>
 __device__ __forceinline__ Dec decode(const uint32_t (&w)[13], uint32_t len32, const uint8_t *hdr, uint32_t p,
-                                      uint32_t stride, uint32_t syn_check, uint32_t stm = 0u) {
+                                      uint32_t n, uint32_t stride, uint32_t syn_check, uint32_t stm = 0u) {
     Dec k;
     const uint32_t len = len32 & 0xffffu;  // Decode passes (uint16_t)pkt_totallen, decode.c:22
     // ---- Ethernet: dataplane/src/decode/decode-ethernet.c:23-115 ----
@@ -392,11 +398,12 @@ __device__ __forceinline__ Dec decode(const uint32_t (&w)[13], uint32_t len32, c
     uint32_t ackw = (D[7] >> 16) | (D[8] & 0xffffu);     // TCP th_ack, L4+8..11 (only tested for non-zero, stm)
     if (l4_in & !fast & !win_short) {  // IPv4 options: L4 header at a data-dependent offset
         uint32_t h0, h1, h2, h6;
-        ld_l4_sync(hdr + (size_t)p * stride + l4off, h0, h1, h2, h6);
+        const uint8_t *l4 = hdr + (size_t)min(p, n - 1u) * stride + l4off;
+        ld_l4_sync(l4, h0, h1, h2, h6);
         sport = bswap16(h0);
         dport = bswap16(h1);
         x = is_tcp ? h6 : bswap16(h2);
-        if (stm && is_tcp) ackw = ld_ack_sync(hdr + (size_t)p * stride + l4off);
+        if (stm && is_tcp) ackw = ld_ack_sync(l4);
     }
     // ---- UDP: dataplane/src/decode/decode-udp.c:16-49;  TCP: dataplane/src/decode/decode-tcp.c:135-190 ----
     const uint32_t thl = ((x & 0xffu) >> 4) << 2;  // uint8_t hlen, decode-tcp.c:148
@@ -558,7 +565,7 @@ __device__ __forceinline__ bool resid_match(uint32_t rs, const uint4 c, const ui
         if (rs & PPE_RESID_SMAC) m = m && c.z == smac_lo && c.w == smac_hi;
     }
     if (rs & PPE_RESID_TIME) {  // the packet timestamp is only fetched for time-window rules
-        const uint64_t ts = tsp ? ld_u64_sync(tsp + p) : now;
+        const uint64_t ts = tsp ? ld_u64_sync(tsp + mac.row(p)) : now;
         const uint64_t t0 = (uint64_t)t.x | ((uint64_t)t.y << 32);
         const uint64_t t1 = (uint64_t)t.z | ((uint64_t)t.w << 32);
         m = m && ts >= t0 && ts <= t1;
@@ -1524,7 +1531,7 @@ void ppe_classify_kernel(ppe_kargs a) {
         const uint32_t p = (tile << 6) + lane;
         const bool valid = p < B.n;
         if (!(PPE_ABLATE & 2) && valid) rx_bytes += wlen;
-        Dec k = decode<!PART>(w, wlen, B.hdr, p, B.stride, a.syn_check, stm);
+        Dec k = decode<!PART>(w, wlen, B.hdr, p, B.n, B.stride, a.syn_check, stm);
 
         uint32_t fh = 0;
         int32_t hit = -1;
@@ -1554,7 +1561,7 @@ void ppe_classify_kernel(ppe_kargs a) {
         }
         if (!(PPE_ABLATE & 1) && k.st == ST_ACL && !CUT) {
             uint32_t rule_act;
-            const MacFromWindow mac = {B.hdr, p, B.stride};
+            const MacFromWindow mac = {B.hdr, p, B.n, B.stride};
             lds_st32(lanebase + 256u * PPE_DIM_SIP, k.sip);
             lds_st32(lanebase + 256u * PPE_DIM_DIP, k.dip);
             lds_st32(lanebase + 256u * PPE_DIM_SPORT, k.sport);
@@ -1583,7 +1590,7 @@ void ppe_classify_kernel(ppe_kargs a) {
             if (p < B.n) rx_bytes += rl[t];
             const uint32_t w[13] = {r0[t].x, r0[t].y, r0[t].z, r0[t].w, r1[t].x, r1[t].y, r1[t].z, r1[t].w,
                                     r2[t].x, r2[t].y, r2[t].z, r2[t].w, r3[t]};
-            Dec d = decode<!PART>(w, rl[t], B.hdr, p, B.stride, a.syn_check, stm);
+            Dec d = decode<!PART>(w, rl[t], B.hdr, p, B.n, B.stride, a.syn_check, stm);
             if ((PPE_ABLATE & 1) && d.st == ST_ACL) {
                 d.st = PPE_ST_ACL_FW;
                 d.flags |= PPE_F_ACL;
@@ -1629,7 +1636,7 @@ void ppe_classify_kernel(ppe_kargs a) {
     auto mt_leaf = [&](uint32_t tile, const uint32_t (&key)[4], const uint4 &nd, int32_t &hit, bool &drop) {
         uint32_t rule_act;
         const uint32_t p = (tile << 6) + lane;
-        const MacFromWindow mac = {B.hdr, p, B.stride};
+        const MacFromWindow mac = {B.hdr, p, B.n, B.stride};
         acl_leaf<MODE, L::IMGB>(a.img, geo, nd, key[0], key[1], key[2] & 0xffffu, key[2] >> 16,
                                 (key[3] >> 16) & 0xffu, mac, B.ts, p, a.now, hit, rule_act);
         drop = rule_act == ACL_RULE_ACTION_DROP;

@@ -88,7 +88,7 @@ __global__ __launch_bounds__(PS_BLOCK) void ps_find_kernel(ppe_ps_kargs a) {
     const uint4 q0 = gld<uint4>(a.hdr, ro), q1 = gld<uint4>(a.hdr, ro + 16u), q2 = gld<uint4>(a.hdr, ro + 32u);
     const uint32_t w12 = gld<uint32_t>(a.hdr, ro + 48u), wlen = gld<uint32_t>(a.len, 4u * pc);
     const uint32_t w[13] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, w12};
-    const Dec k = decode<false>(w, wlen, a.hdr, pc, a.stride, a.syn_check);
+    const Dec k = decode<false>(w, wlen, a.hdr, pc, a.n, a.stride, a.syn_check);
     // flow.c:204-215: the packet reaches PortScan_Detect iff it would reach DP_Acl_Lookup
     const bool elig = i < a.n && k.st == ST_ACL;
     uint32_t slot = PPE_PS_NOSLOT;

@@ -14,6 +14,8 @@ import pyoracle  # noqa: E402
 from ppe import Engine, abi, synth  # noqa: E402
 from test_gpu_parity import check_compaction, check_part8, check_partition  # noqa: E402
 
+import decode_corpus as dc  # noqa: E402
+
 DEV = torch.device("cuda:0")
 NOW = 1_000_000
 
@@ -283,3 +285,28 @@ def test_flow_argument_errors(eng):
     b.n = 64
     assert lib.ppe_classify_flow(eng.ctx, C.byref(b), C.byref(r), C.byref(eng.cfg()), None) == -22  # no verdict
     eng.flow_destroy()
+
+
+@pytest.mark.parametrize("nrules", [256, 4096])
+@pytest.mark.parametrize("stride", [96, 128, 256])
+def test_flow_decode_edge_corpus(eng, nrules, stride):
+    """The decode edge corpus (tests/decode_corpus.py: both sides of every comparator of the decode, IPv4 header
+    lengths 5 to 15 under every L2 tagging) through the FLOW kernels, at windows that hold every header of it (no
+    WINDOW_PUNT, so the oracle's table and the engine's see the same packets): the corpus, the corpus rolled by 37
+    (every flow found, in another tile and lane), and the corpus with addresses and ports swapped (the other direction);
+    per-packet outputs, counters and the dumped table after each batch."""
+    rules = synth.make_rules(nrules, seed=nrules)
+    hdr, lens, _ = dc.corpus(rules)
+    rhdr, rlens, _ = dc.corpus(rules, reverse=True)
+    batches = ((hdr, lens), (np.roll(hdr, 37, axis=0), np.roll(lens, 37)), (rhdr, rlens))
+    p = Pair(eng, rules, capacity=10000, max_batch=4096, default_action=0)
+    try:
+        new = []
+        for b, (h, l) in enumerate(batches):
+            got, ref = p.batch(np.ascontiguousarray(h[:, :stride]), l, NOW + b, part=(False, True, "8")[b])
+            new.append(p.same_table()["new_flow"])
+        assert new[0] > 400 and new[1] == new[0] and new[2] > new[1]  # created, all found, some more created
+        assert (((ref["verdict"] >> 16) & abi.F_TOCLIENT) != 0).sum() > 400
+    finally:
+        p.close()
+

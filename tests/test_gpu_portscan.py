@@ -14,6 +14,7 @@ pytestmark = pytest.mark.gpu
 import torch  # noqa: E402  (loads the HIP runtime first)
 
 import pyoracle  # noqa: E402
+import decode_corpus as dc  # noqa: E402
 import stream_model as sm  # noqa: E402
 from pktbuild import ip_frag, tcp_packet, udp_packet  # noqa: E402
 from portscan_model import DETECTED, HOLD, NOMEM, OK, PortScanModel  # noqa: E402
@@ -520,3 +521,23 @@ def test_not_supported_calls_leave_everything_usable(eng):
     finally:
         eng.flow_destroy()
         rig.close()
+
+
+@pytest.mark.parametrize("nrules", [256, 4096])
+@pytest.mark.parametrize("stream", [None, (1, 0, 0)], ids=["plain", "stream"])
+@pytest.mark.parametrize("syn_check", [1, 0])
+def test_decode_edge_corpus(eng, syn_check, stream, nrules):
+    """The pre-pass decodes every packet itself: its eligibility must equal "reached the ACL" on every edge of the
+    decode (tests/decode_corpus.py, 128-B windows: nothing punts).  One frame, 64 frames from an odd offset, then the
+    whole corpus, into a table of 40 records that every eligible packet trips (exception_freq 0)."""
+    rules = synth.make_rules(nrules, seed=nrules)
+    hdr, lens, _ = dc.corpus(rules)
+    hdr = np.ascontiguousarray(hdr[:, :128])
+    rig = Rig(eng, rules, stream=stream, syn_check=syn_check, exception_freq=0, capacity=40)
+    try:
+        for lo, hi in ((0, 1), (1, 65), (0, len(lens))):
+            got, exp = rig.step(hdr[lo:hi], lens[lo:hi], outs=SEP if hi - lo > 64 else PART)
+        assert ((exp["verdict"] & 0xFF) == ST["PORTSCAN_DROP"]).any()
+    finally:
+        rig.close()
+

@@ -15,6 +15,7 @@ pytestmark = pytest.mark.gpu
 import torch  # noqa: E402  (loads the HIP runtime first)
 
 import pyoracle  # noqa: E402
+import decode_corpus as dc  # noqa: E402
 import stream_model as sm  # noqa: E402
 from ppe import Engine, PPEError, abi, synth  # noqa: E402
 from ppe.abi import ST  # noqa: E402
@@ -419,3 +420,49 @@ def test_errors(eng):
     finally:
         eng.flow_destroy()
         ft.close()
+
+
+def corpus_case(rules_name, stride, syn_check):
+    """The decode edge corpus (tests/decode_corpus.py) through a stride-wide window and the oracle's answer for it
+    (tracking off), computed once per case and left unchanged."""
+    key = ("corpus", rules_name, stride, syn_check)
+    if key not in _cache:
+        rules, dflt = ruleset(rules_name)
+        if ("corpus", rules_name) not in _cache:
+            _cache[("corpus", rules_name)] = dc.corpus(rules)
+        hdr, lens, _ = _cache[("corpus", rules_name)]
+        pk = dict(hdr=np.ascontiguousarray(hdr[:, :stride]), len=lens)
+        o = pyoracle.Oracle(rules, default_action=dflt)
+        ref = o.classify_batch(pk["hdr"], pk["len"], cfg=o.cfg(0, syn_check, NOW))
+        for v in ref.values():
+            v.setflags(write=False)
+        _cache[key] = (pk, ref)
+    return _cache[key]
+
+
+@pytest.mark.parametrize("tune", [dict(), dict(pipeline=3), dict(pipeline=5)],
+                         ids=lambda d: ",".join(f"{k}={v}" for k, v in d.items()) or "default")
+@pytest.mark.parametrize("cfg", [REF_DEFAULT, ONESIDE], ids=["default", "oneside"])
+@pytest.mark.parametrize("stride", [128, 64])
+def test_decode_edge_corpus(eng, tune, cfg, stride):
+    """TCP flag bytes and th_ack behind every IPv4 header length 5 to 15 and both tag types (the slow path's reads of
+    them), next to every malformed neighbour of such a frame: the decode edge corpus with tracking on.  At stride 64
+    the frames behind long options are WINDOW_PUNTs, excluded as for the sweep."""
+    for rules_name in ("256", "4096"):
+        rules, dflt = ruleset(rules_name)
+        eng.commit(rules, default_action=dflt)
+        eng.stream_tcp(*cfg)
+        old = eng.tuning()
+        try:
+            eng.tuning(**tune)
+            for syn_check in (1, 0):
+                pk, ref = corpus_case(rules_name, stride, syn_check)
+                for outs in (SEP, PART):
+                    got, exp = check_against_model(eng, pk, ref, cfg, stride, outs, syn_check)
+                assert exp["stream"]["syn_count"] > 0 and exp["stream"]["syn_ack_count"] > 0
+                if syn_check == 0:
+                    assert exp["stream"]["rst_but_no_session"] > 0 and exp["stream"]["fin_but_no_session"] > 0
+                    assert exp["stream"]["midstream_disable"] > 0 and exp["stream"]["pkt_broken_ack"] > 0
+        finally:
+            eng.tuning(**old)
+
