@@ -40,7 +40,9 @@ extern "C" {
  * 6: ppe_acl_stats_t cut fields; 7: ppe_rules_stage / _publish; 8: ppe_result_t.packed (8-B verdict + flow hash +
  * ACL hit); additive within 8 (no existing struct or value changes): the StreamTcp first-packet verdict
  * (ppe_stream_tcp_*, statuses 20-23, ppe_stream_counters_*, ppe_format_tcpstream_stat), off until set; the port-scan
- * detector (ppe_portscan_*, status 24, ppe_format_pkt_stat_ps, ppe_format_fw_config), off until a table is attached */
+ * detector (ppe_portscan_*, status 24, ppe_format_pkt_stat_ps, ppe_format_fw_config), off until a table is attached;
+ * the land / SYN-flood / UDP-flood monitors (ppe_attack_*, statuses 25-28, ppe_format_attack_stat,
+ * ppe_format_pkt_stat_atk), off until an object is attached */
 #define PPE_ABI_VERSION 8
 
 /* error codes (negative return values) */
@@ -88,7 +90,15 @@ enum ppe_status {
     /* PPE_ST__COUNT keeps its value: the statuses a context without a port-scan table produces (0-23; bindings and
      * tables sized by it stay valid).  PPE_ST__END counts every status, PPE_ST_PORTSCAN_DROP included. */
     PPE_ST__COUNT = 24,
-    PPE_ST__END = 25
+    PPE_ST__END = 25,
+    /* The attack monitors of dataplane/src/attack/dp_attack.c, only with an object attached (ppe_attack_attach).  All
+     * four drop before the L4 decoders finish and before FlowHandlePacket: acl_hit -1, PPE_F_ACL and PPE_F_L4 clear,
+     * flow hash 0, tuple word 2 zero, word 3 = proto | vlan << 8; PPE_F_TCP | PPE_F_SYN set on 25-27, neither on 28. */
+    PPE_ST_ATTACK_LAND = 25,      /* TCP SYN with sip == dip       STAT_ATTACK_LAND           dp_attack.c:464-484 */
+    PPE_ST_ATTACK_SYNFLOOD = 26,  /* SYN-flood hold or speed       STAT_ATTACK_SYNFLOOD_DROP  dp_attack.c:637-670 */
+    PPE_ST_ATTACK_SYNCOUNT = 27,  /* syncount above syn_count      STAT_ATTACK_SYNCOUNT       dp_attack.c:673-685 */
+    PPE_ST_ATTACK_UDPFLOOD = 28,  /* UDP-flood hold or speed       STAT_ATTACK_UDPFLOOD_DROP  dp_attack.c:582-634 */
+    PPE_ST__ALL = 29              /* every status, the monitors' included (PPE_ST__END keeps its value) */
 };
 
 enum ppe_action { PPE_ACT_FW = 0, PPE_ACT_DROP = 1, PPE_ACT_PUNT = 2 };
@@ -580,6 +590,87 @@ int  ppe_portscan_dump(ppe_portscan_t *ps, ppe_portscan_entry_t *entries, uint32
 const char *ppe_portscan_last_error(ppe_portscan_t *ps);
 
 
+/* ---- Land, SYN-flood and UDP-flood monitors on the stateless classify path (dataplane/src/attack/dp_attack.c) ----
+ * All state is per input port (attrule.*[input], attinfo.ai[input]; OCT_PHY_PORT_MAX = 4, oct-port.h:14).  Every
+ * enable test of the reference is `== 1` (ATTACK_ENABLE), so a field holding 2 is off, and drop_pack == 1 means drop.
+ * With an object attached, ppe_classify and ppe_classify_batches run, per packet:
+ *   UDP (decode-ipv4.c:141-149, dp_attack.c:582-634), for every non-fragment protocol-17 packet that passed the IPv4
+ *   checks, before DecodeUDP (a bad UDP header is counted and may be flood-dropped before its length is looked at):
+ *     udp_accum++; flood_udp == 1 && drop_pack == 1 && (udp_flood_hold || udppps > udp_speed) → PPE_ST_ATTACK_UDPFLOOD
+ *     (the speed branch sets udp_flood_hold = 1, udp_flood_hold_time = now_seconds + hold_seconds when not yet held);
+ *   TCP SYN (decode-tcp.c:162-173), for a TCP packet that passed the three length checks with th_flags & 0x02 (a
+ *   SYN|ACK counts): pd.land == 1 && sip == dip && pd.drop_pack == 1 → PPE_ST_ATTACK_LAND (not added to syn_accum);
+ *     else syn_accum++; the hold / speed branches as for UDP with flood_syn, synpps, syn_speed →
+ *     PPE_ST_ATTACK_SYNFLOOD; else syncount > syn_count && td.drop_pack == 1 → PPE_ST_ATTACK_SYNCOUNT (not gated by
+ *     flood_syn).
+ *   syncount_accum++ (FlowAdd, flow.c:151-154) for every TCP SYN packet whose status is PPE_ST_ACL_FW after the
+ *   port-scan mask and before StreamTcp's verdict: on this path every packet that reaches FlowAdd is the first of its
+ *   flow.  The decrements (stream-tcp.c:608,660, stream-tcp-session.c:70) belong to the session machine: not built.
+ * Not judged and not counted: fragments, PPE_ST_WINDOW_PUNT, anything that fails before the IPv4 protocol dispatch,
+ * a TCP packet that fails a length check or has no SYN.  A reassembled datagram classified afterwards counts once (the
+ * reference adds one per fragment, dp_attack.c:586-601: a known difference).  ICMP never reaches its monitors in the
+ * reference build, and the teardrop monitor is ppe_defrag's: their rule fields are stored and shown, not acted on.
+ * A monitor drop counts in ppe_counters_t the RX_OK chain up to IPV4_RX_OK, OUT_DROP, PKTS and RX_BYTES; nothing of
+ * UDP / TCP / ACL / FLOW.  A monitor-dropped packet never reaches the port-scan detector or StreamTcp.
+ * Between two ticks everything a verdict reads is constant (the hold flags change only on a packet dropped either
+ * way), so the verdicts equal one core's processing the packets in any order.
+ * The clock (OCT_TIME_SECONDS_SINCE1970) is the caller's: ppe_attack_clock / ppe_attack_tick, not batch.ts.
+ * ppe_attack_set, _tick and _clear_stat are tiny kernels enqueued on the stream of the context's latest classify call
+ * (the legacy default stream before the first): ordered with the launches enqueued before and after, no
+ * synchronisation.  The caller orders its classify calls (one stream), as with the port-scan table.
+ * With an object attached ppe_classify_flow and ppe_classify_host return PPE_ENOTSUP before touching anything.
+ * A new context has nothing attached: every output and counter is as without this interface. */
+#define PPE_ATTACK_PORTS 4
+typedef struct {                 /* packet_detect (dp_attack.h:26-33) */
+    uint32_t drop_pack, land, teardrop, pingdeath, pingdeath_value;
+} ppe_attack_pd_t;
+typedef struct {                 /* traffic_detect (dp_attack.h:35-48) */
+    uint32_t drop_pack, flood_ping, ping_speed, last_ping_flood_time, flood_udp, udp_speed, last_udp_flood_time,
+             flood_syn, syn_speed, last_syn_flood_time, syn_count;
+} ppe_attack_td_t;
+typedef struct {
+    ppe_attack_pd_t pd[PPE_ATTACK_PORTS];
+    ppe_attack_td_t td[PPE_ATTACK_PORTS];
+    uint32_t hold_seconds;       /* flood_hold_time (dp_attack.c:25) */
+    uint32_t pad;
+} ppe_attack_cfg_t;
+typedef struct {                 /* attack_info (dp_attack.h:73-89); the ping fields stay 0 */
+    uint64_t pingpps, ping_accum, udppps, udp_accum, synpps, syn_accum, syncount, syncount_accum;
+    uint64_t ping_flood_hold, ping_flood_hold_time, syn_flood_hold, syn_flood_hold_time, udp_flood_hold,
+             udp_flood_hold_time;
+} ppe_attack_port_t;
+typedef struct {
+    ppe_attack_cfg_t cfg;        /* the rules in force */
+    ppe_attack_port_t ai[PPE_ATTACK_PORTS];
+    uint64_t land_drop, udpflood_drop, synflood_drop, syncount_drop;   /* attstat.land / udpspeed / synspeed / syncount */
+    uint64_t now_seconds;        /* the clock the next launch takes */
+} ppe_attack_info_t;
+
+typedef struct ppe_attack ppe_attack_t;
+/* cfg NULL: all-zero rules and hold_seconds 600 (DP_Attack_Del_All, flood_hold_time) */
+int  ppe_attack_create(ppe_ctx_t *ctx, const ppe_attack_cfg_t *cfg, ppe_attack_t **out);
+/* detaches it from its context first.  Destroy the object before its context: it keeps a pointer to the context, and
+ * ppe_ctx_destroy neither detaches nor destroys it (the same holds for ppe_portscan_destroy) */
+int  ppe_attack_destroy(ppe_attack_t *atk);
+int  ppe_attack_attach(ppe_ctx_t *ctx, ppe_attack_t *atk);        /* NULL detaches */
+/* the rule file load / DP_Attack_Del_All / dp_attack_defend_time_set: the rules and hold_seconds (the state stays) */
+int  ppe_attack_set(ppe_attack_t *atk, const ppe_attack_cfg_t *cfg);
+int  ppe_attack_clock(ppe_attack_t *atk, uint64_t now_seconds);   /* by value with the launches enqueued afterwards */
+/* DP_Attack_Info_Update (dp_attack.c:712-748; the reference runs it once a second, watchdog.c:117-122): per port
+ * pps = accum, accum = 0; now >= hold_time clears both hold fields (also when nothing is held); sets the clock too */
+int  ppe_attack_tick(ppe_attack_t *atk, uint64_t now_seconds);
+/* Sticky: device array ports[k] holds one byte per packet, the input port of each packet of batch k of every later
+ * classify call (ppe_classify: k = 0).  ports NULL, ports[k] NULL or k >= nbatch: port 0 for every packet.  The kernels
+ * use port & 3, so nothing is indexed past four ports; values >= 4 are the caller's error.  nbatch <= 4096.
+ * Not a hot-path call: it allocates a new device table and copies the pointers synchronously; the table it replaces
+ * is freed once the launches enqueued before the call (on the classify stream) have completed. */
+int  ppe_attack_ports(ppe_attack_t *atk, const uint8_t *const *ports, uint32_t nbatch);
+int  ppe_attack_info(ppe_attack_t *atk, ppe_attack_info_t *info);   /* synchronises */
+int  ppe_attack_clear_stat(ppe_attack_t *atk);                      /* the four drop totals only */
+const char *ppe_attack_last_error(ppe_attack_t *atk);
+/* `show attack stat` text (dp_show_attack_stat, dp_cmd.c:2394-2529) byte for byte; snprintf semantics */
+int  ppe_format_attack_stat(const ppe_attack_info_t *info, char *buf, size_t cap);
+
 /* `show packet statistic` / `show flow statistic` text (dp_show_pkt_stat / dp_show_flow_stat,
  * dataplane/src/common/dp_cmd.c:844-1818, 2346-2392) into buf (NUL-terminated, truncated to cap); returns the full
  * length.  The _ex forms take the IPv4 reassembly table's counters (NULL: those lines print 0, as the plain forms
@@ -596,6 +687,11 @@ int  ppe_format_pkt_stat_ps(const ppe_counters_t *c, const ppe_defrag_info_t *df
 /* the four port-scan lines of `show fw config` (dp_cmd.c:2578-2590): detect stat, detect action, flood hold time,
  * portscan_exception_freq.  cfg NULL = the reference defaults. */
 int  ppe_format_fw_config(const ppe_portscan_cfg_t *cfg, char *buf, size_t cap);
+/* ppe_format_pkt_stat_ps with the attack section's land_drop / udp flood drop / syn flood drop / syncount lines from
+ * atk_info's drop totals (NULL: 0, as the older forms print) */
+int  ppe_format_pkt_stat_atk(const ppe_counters_t *c, const ppe_defrag_info_t *df, int teardrop_monitor,
+                             const ppe_portscan_info_t *ps_info, const ppe_attack_info_t *atk_info, char *buf,
+                             size_t cap);
 const char *ppe_defrag_last_error(ppe_defrag_t *d);
 
 /* Human-readable last error of this context (static storage of the ctx). */

@@ -127,6 +127,22 @@ struct ppe_portscan_table {
     char err[256] = {0};
 };
 
+// ppe_attack_create: the attack monitors' rules, clock and device state (csrc/ppe_attack.hip, ppe_internal.h PPE_ATK_*)
+struct ppe_attack {
+    ppe_ctx *ctx = nullptr;
+    ppe_attack_cfg_t cfg = {};
+    uint64_t now = 0;                       // ppe_attack_clock / _tick
+    unsigned long long *d_st = nullptr;     // [PPE_ATK_WORDS]
+    unsigned long long *d_slots = nullptr;  // [ctx->max_grid][PPE_ATK_SLOT_WORDS] the classify workgroups' count slots
+    const uint8_t **d_ports = nullptr;      // ppe_attack_ports: the device table launches read, or NULL
+    std::vector<const uint8_t *> h_ports;   // its host copy (the port-scan pre-pass takes a batch's pointer by value)
+    struct Retired { void *p; hipEvent_t done; };
+    std::vector<Retired> retired;           // earlier tables, which launches in flight may still read: each is freed once
+                                            // the event recorded behind the last launch that could read it has completed
+    hipStream_t stream = nullptr;           // the context's latest classify stream: set / tick / clear go there
+    char err[256] = {0};
+};
+
 struct ppe_ctx {
     int device = 0;
     uint32_t n_cu = 256;
@@ -183,6 +199,7 @@ struct ppe_ctx {
     // / 8 / 32 groups 20.2 / 18.7 / 18.3 / 18.3 / 19.1 us (one run, tools/ab_bench.py)
     uint32_t max_groups = 8;
     ppe_portscan_table *ps = nullptr;  // ppe_portscan_attach
+    ppe_attack *atk = nullptr;         // ppe_attack_attach
     FlowTable *flow = nullptr;  // ppe_flow_create
     LookupStage lk;             // ppe_acl_lookup_host
     uint32_t *d_steer = nullptr;  // ppe_steer_partition: per-tile owner counts / offsets
@@ -531,7 +548,8 @@ int ps_rebuild(ppe_portscan_table *t, int age, uint64_t now_cycles) {
 
 // PortScan_Detect for batches in[0, nb) in order on stream s (csrc/ppe_portscan.hip), their drop masks one after the
 // other in t->mask
-int ps_prepass(ppe_ctx *c, const ppe_batch_t *in, uint32_t nb, const ppe_cfg_t *cfg, hipStream_t s) {
+int ps_prepass(ppe_ctx *c, const ppe_batch_t *in, uint32_t nb, const ppe_cfg_t *cfg, hipStream_t s,
+               uint32_t atk_pbase) {
     ppe_portscan_table *t = c->ps;
     size_t words = 0;
     for (uint32_t i = 0; i < nb; ++i) {
@@ -589,6 +607,11 @@ int ps_prepass(ppe_ctx *c, const ppe_batch_t *in, uint32_t nb, const ppe_cfg_t *
         a.cbase = t->cbase;
         a.work = t->work;
         a.mask = t->mask + off;
+        if (c->atk) {  // a packet the attack monitors drop never reaches the detector
+            a.atk_st = c->atk->d_st;
+            const size_t k = (size_t)atk_pbase + i;
+            a.atk_ports = k < c->atk->h_ports.size() ? c->atk->h_ports[k] : nullptr;
+        }
         off += (n + 63u) / 64u;
         static const int pre[] = {PPE_PS_K_FIND, PPE_PS_K_CREATORS, PPE_PS_K_SCAN, PPE_PS_K_GRANT, PPE_PS_K_KEYS,
                                   PPE_PS_K_SORT_LDS};
@@ -611,7 +634,7 @@ int ps_prepass(ppe_ctx *c, const ppe_batch_t *in, uint32_t nb, const ppe_cfg_t *
 // of batch 1, ... (no barrier between batches, one image staging for all of them).
 int launch(ppe_ctx *c, const ppe_batch_t *in, const ppe_result_t *out, uint32_t nb, const ppe_cfg_t *cfg,
            hipStream_t s, int slot_set, uint32_t idx_base = 0, const ppe_flowdev *fl = nullptr,
-           uint32_t *grid_out = nullptr) {
+           uint32_t *grid_out = nullptr, uint32_t atk_pbase = 0) {
     const int r = c->running;
     const ppe_plan &plan = c->plan[r][fl != nullptr];
     ppe_kargs a;
@@ -626,9 +649,20 @@ int launch(ppe_ctx *c, const ppe_batch_t *in, const ppe_result_t *out, uint32_t 
     int rc = fill_descs(c, r, in, out, nb, idx_base, fl != nullptr, use_ring ? c->ring_tmp.data() : a.batch, sh, psc);
     if (rc != PPE_OK) return rc;
     if (psc) {  // PortScan_Detect for every batch, in order, ahead of the launch on its stream
-        rc = ps_prepass(c, in, nb, cfg, s);
+        rc = ps_prepass(c, in, nb, cfg, s, atk_pbase);
         if (rc != PPE_OK) return rc;
         a.psmask = c->ps->mask;
+    }
+    if (ppe_pick_attack(fl != nullptr, c->atk != nullptr)) {  // the monitors: rules and state on the device, clock by value
+        ppe_attack *t = c->atk;
+        a.atk_st = t->d_st;
+        a.atk_slots = t->d_slots;
+        a.atk_ports = t->d_ports;
+        a.atk_nports = (uint32_t)t->h_ports.size();
+        a.atk_pbase = atk_pbase;
+        a.atk_now = t->now;
+        a.atk_hold = t->cfg.hold_seconds;
+        t->stream = s;
     }
     int rslot = 0;
     if (use_ring) {
@@ -893,6 +927,28 @@ int ppe_classify_batches(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t
     uint32_t nonempty = 0;
     for (uint32_t i = 0; i < nbatch; ++i) nonempty += in[i].n != 0;
     if (nonempty == 0) return PPE_OK;
+    if (c->atk) {
+        // attack monitors: the launches go one after the other on the caller's stream; a launch takes consecutive
+        // batches of the call (an empty one ends it), so batch k keeps its port array ppe_attack_ports gave it
+        std::vector<ppe_batch_t> gin;
+        std::vector<ppe_result_t> gout;
+        uint32_t base = 0;
+        for (uint32_t i = 0; i <= nbatch; ++i) {
+            if (i < nbatch && in[i].n) {
+                if (gin.empty()) base = i;
+                gin.push_back(in[i]);
+                gout.push_back(out[i]);
+            }
+            if (!gin.empty() && (i == nbatch || in[i].n == 0 || gin.size() == per)) {
+                const int rc = launch(c, gin.data(), gout.data(), (uint32_t)gin.size(), cfg, s, 0, 0, nullptr, nullptr,
+                                      base);
+                if (rc != PPE_OK) return rc;
+                gin.clear();
+                gout.clear();
+            }
+        }
+        return PPE_OK;
+    }
     if (nonempty <= per) {  // one launch: straight onto the caller's stream, no fork / join
         std::vector<ppe_batch_t> gin;
         std::vector<ppe_result_t> gout;
@@ -979,6 +1035,8 @@ int ppe_classify_host(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *o
     if (!c || !out) return PPE_EINVAL;
     // the chunks of the staged path run on several streams; the detector needs the packets in order on one
     if (c->ps) return fail(c, PPE_ENOTSUP, "ppe_classify_host with a port-scan table attached is not supported");
+    // the same for the attack monitors: their hold and their clock follow the order of the launches on one stream
+    if (c->atk) return fail(c, PPE_ENOTSUP, "ppe_classify_host with attack monitors attached is not supported");
     int rc = check_batch(c, in, cfg);
     if (rc != PPE_OK || in->n == 0) return rc;
     HIPCHK(c, hipSetDevice(c->device));
@@ -1391,6 +1449,227 @@ int ppe_portscan_dump(ppe_portscan_t *t, ppe_portscan_entry_t *entries, uint32_t
 
 const char *ppe_portscan_last_error(ppe_portscan_t *t) { return t ? t->err : "null port-scan table"; }
 
+// ---- attack monitors (dataplane/src/attack/dp_attack.c) ----
+static int atk_fail(ppe_attack *t, int code, const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(t->err, sizeof t->err, fmt, ap);
+    va_end(ap);
+    if (t->ctx) std::snprintf(t->ctx->err, sizeof t->ctx->err, "%s", t->err);
+    return code;
+}
+#define ATKCHK(t, expr)                                                                               \
+    do {                                                                                              \
+        hipError_t e_ = (hipError_t)(expr);                                                           \
+        if (e_ != hipSuccess) return atk_fail((t), PPE_EIO, "%s: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+
+// all = true: after a device synchronise; else only the tables whose event has completed
+static void atk_free_retired(ppe_attack *t, bool all) {
+    size_t keep = 0;
+    for (auto &r : t->retired) {
+        if (all || !r.done || hipEventQuery(r.done) == hipSuccess) {
+            (void)hipFree(r.p);
+            if (r.done) (void)hipEventDestroy(r.done);
+        } else {
+            t->retired[keep++] = r;
+        }
+    }
+    t->retired.resize(keep);
+    (void)hipGetLastError();  // (hipErrorNotReady of a pending event is no error of the caller's)
+}
+
+// the rules reduced to what the monitors read; every test of the reference is == ATTACK_ENABLE (1)
+static void atk_rule_args(const ppe_attack_cfg_t &v, ppe_atk_kargs &a) {
+    for (int p = 0; p < PPE_ATTACK_PORTS; ++p) {
+        const ppe_attack_pd_t &pd = v.pd[p];
+        const ppe_attack_td_t &td = v.td[p];
+        a.rule[p][0] = ((pd.land == 1u && pd.drop_pack == 1u) ? PPE_ATK_EN_LAND : 0u) |
+                       ((td.flood_udp == 1u && td.drop_pack == 1u) ? PPE_ATK_EN_UDP : 0u) |
+                       ((td.flood_syn == 1u && td.drop_pack == 1u) ? PPE_ATK_EN_SYN : 0u) |
+                       (td.drop_pack == 1u ? PPE_ATK_EN_DROP : 0u);
+        a.rule[p][1] = td.udp_speed;
+        a.rule[p][2] = td.syn_speed;
+        a.rule[p][3] = td.syn_count;
+    }
+}
+
+int ppe_attack_create(ppe_ctx_t *c, const ppe_attack_cfg_t *cfg, ppe_attack_t **out) {
+    if (!c || !out) return PPE_EINVAL;
+    *out = nullptr;
+    HIPCHK(c, hipSetDevice(c->device));
+    ppe_attack *t = new ppe_attack;
+    t->ctx = c;
+    if (cfg) t->cfg = *cfg;
+    else t->cfg.hold_seconds = 600u;  // flood_hold_time (dp_attack.c:25); the rules all zero (DP_Attack_Del_All)
+    t->cfg.pad = 0;
+    ppe_atk_kargs a;
+    std::memset(&a, 0, sizeof a);
+    atk_rule_args(t->cfg, a);
+    a.op = PPE_ATK_K_SET;
+    const size_t slot_bytes = (size_t)c->max_grid * PPE_ATK_SLOT_WORDS * 8u;
+    bool ok = hipMalloc(&t->d_st, PPE_ATK_WORDS * 8u) == hipSuccess &&
+              hipMemset(t->d_st, 0, PPE_ATK_WORDS * 8u) == hipSuccess && hipMalloc(&t->d_slots, slot_bytes) == hipSuccess &&
+              hipMemset(t->d_slots, 0, slot_bytes) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+    a.st = t->d_st;
+    ok = ok && ppe_launch_attack_ctl(&a, nullptr) == 0 && hipDeviceSynchronize() == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        if (t->d_st) (void)hipFree(t->d_st);
+        if (t->d_slots) (void)hipFree(t->d_slots);
+        delete t;
+        return fail(c, PPE_ENOMEM, "ppe_attack_create: no device memory, or the first rule load failed");
+    }
+    *out = t;
+    return PPE_OK;
+}
+
+int ppe_attack_destroy(ppe_attack_t *t) {
+    if (!t) return PPE_EINVAL;
+    (void)hipSetDevice(t->ctx->device);
+    (void)hipDeviceSynchronize();
+    if (t->ctx->atk == t) t->ctx->atk = nullptr;
+    atk_free_retired(t, true);
+    if (t->d_ports) (void)hipFree((void *)t->d_ports);
+    (void)hipFree(t->d_st);
+    (void)hipFree(t->d_slots);
+    delete t;
+    return PPE_OK;
+}
+
+int ppe_attack_attach(ppe_ctx_t *c, ppe_attack_t *t) {
+    if (!c) return PPE_EINVAL;
+    if (t && t->ctx != c) return fail(c, PPE_EINVAL, "ppe_attack_attach: the object belongs to another context");
+    c->atk = t;
+    return PPE_OK;
+}
+
+int ppe_attack_set(ppe_attack_t *t, const ppe_attack_cfg_t *cfg) {
+    if (!t || !cfg) return PPE_EINVAL;
+    ATKCHK(t, hipSetDevice(t->ctx->device));
+    ppe_atk_kargs a;
+    std::memset(&a, 0, sizeof a);
+    atk_rule_args(*cfg, a);
+    a.st = t->d_st;
+    a.op = PPE_ATK_K_SET;
+    ATKCHK(t, ppe_launch_attack_ctl(&a, t->stream));
+    t->cfg = *cfg;  // hold_seconds travels by value with the launches enqueued from now on
+    t->cfg.pad = 0;
+    return PPE_OK;
+}
+
+int ppe_attack_clock(ppe_attack_t *t, uint64_t now_seconds) {
+    if (!t) return PPE_EINVAL;
+    t->now = now_seconds;
+    return PPE_OK;
+}
+
+int ppe_attack_tick(ppe_attack_t *t, uint64_t now_seconds) {
+    if (!t) return PPE_EINVAL;
+    ATKCHK(t, hipSetDevice(t->ctx->device));
+    ppe_atk_kargs a;
+    std::memset(&a, 0, sizeof a);
+    a.st = t->d_st;
+    a.slots = t->d_slots;
+    a.nslots = t->ctx->max_grid;
+    a.op = PPE_ATK_K_TICK;
+    a.now = now_seconds;
+    ATKCHK(t, ppe_launch_attack_ctl(&a, t->stream));
+    t->now = now_seconds;
+    return PPE_OK;
+}
+
+int ppe_attack_ports(ppe_attack_t *t, const uint8_t *const *ports, uint32_t nbatch) {
+    if (!t) return PPE_EINVAL;
+    if (!ports) nbatch = 0;
+    if (nbatch > PPE_MAX_RING) return atk_fail(t, PPE_EINVAL, "ppe_attack_ports: more than %d batches", PPE_MAX_RING);
+    ATKCHK(t, hipSetDevice(t->ctx->device));
+    // launches in flight may still read the table in use: it is retired, not rewritten
+    const uint8_t **nt = nullptr;
+    if (nbatch) {
+        ATKCHK(t, hipMalloc(&nt, (size_t)nbatch * sizeof(*nt)));
+        const hipError_t e = hipMemcpy((void *)nt, ports, (size_t)nbatch * sizeof(*nt), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree((void *)nt);
+            return atk_fail(t, PPE_EIO, "ppe_attack_ports: %s", hipGetErrorString(e));
+        }
+    }
+    if (t->d_ports) {
+        // behind every launch enqueued so far on the classify stream; no event: kept until the next synchronise
+        hipEvent_t ev = nullptr;
+        if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess || hipEventRecord(ev, t->stream) != hipSuccess) {
+            if (ev) (void)hipEventDestroy(ev);
+            ev = nullptr;
+            (void)hipGetLastError();
+            (void)hipDeviceSynchronize();
+        }
+        t->retired.push_back({(void *)t->d_ports, ev});
+    }
+    atk_free_retired(t, false);
+    t->d_ports = nt;
+    t->h_ports.assign(ports, ports + nbatch);
+    return PPE_OK;
+}
+
+int ppe_attack_info(ppe_attack_t *t, ppe_attack_info_t *info) {
+    if (!t || !info) return PPE_EINVAL;
+    ATKCHK(t, hipSetDevice(t->ctx->device));
+    ATKCHK(t, hipDeviceSynchronize());
+    atk_free_retired(t, true);
+    unsigned long long h[PPE_ATK_WORDS];
+    ATKCHK(t, hipMemcpy(h, t->d_st, sizeof h, hipMemcpyDeviceToHost));
+    // what the classify workgroups counted since the last tick is still in their slots
+    std::vector<unsigned long long> sl((size_t)t->ctx->max_grid * PPE_ATK_SLOT_WORDS);
+    ATKCHK(t, hipMemcpy(sl.data(), t->d_slots, sl.size() * 8u, hipMemcpyDeviceToHost));
+    for (size_t b = 0; b < t->ctx->max_grid; ++b) {
+        const unsigned long long *q = &sl[b * PPE_ATK_SLOT_WORDS];
+        for (int p = 0; p < PPE_ATTACK_PORTS; ++p) {
+            unsigned long long *s = h + PPE_ATK_PORT0 + PPE_ATK_PORT_STRIDE * p;
+            s[PPE_ATK_UDP_ACCUM] += q[3 * p];
+            s[PPE_ATK_SYN_ACCUM] += q[3 * p + 1];
+            s[PPE_ATK_SYNCNT_ACCUM] += q[3 * p + 2];
+            h[PPE_ATK_TOTALS + p] += q[12 + p];
+        }
+    }
+    std::memset(info, 0, sizeof *info);
+    info->cfg = t->cfg;
+    for (int p = 0; p < PPE_ATTACK_PORTS; ++p) {
+        const unsigned long long *s = h + PPE_ATK_PORT0 + PPE_ATK_PORT_STRIDE * p;
+        ppe_attack_port_t &o = info->ai[p];
+        o.udppps = s[PPE_ATK_UDPPPS];
+        o.udp_accum = s[PPE_ATK_UDP_ACCUM];
+        o.synpps = s[PPE_ATK_SYNPPS];
+        o.syn_accum = s[PPE_ATK_SYN_ACCUM];
+        o.syncount = s[PPE_ATK_SYNCNT];
+        o.syncount_accum = s[PPE_ATK_SYNCNT_ACCUM];
+        o.syn_flood_hold = s[PPE_ATK_SYN_HOLD];
+        o.syn_flood_hold_time = s[PPE_ATK_SYN_HOLD_TIME];
+        o.udp_flood_hold = s[PPE_ATK_UDP_HOLD];
+        o.udp_flood_hold_time = s[PPE_ATK_UDP_HOLD_TIME];
+    }
+    info->land_drop = h[PPE_ATK_TOTALS + 0];
+    info->udpflood_drop = h[PPE_ATK_TOTALS + 1];
+    info->synflood_drop = h[PPE_ATK_TOTALS + 2];
+    info->syncount_drop = h[PPE_ATK_TOTALS + 3];
+    info->now_seconds = t->now;
+    return PPE_OK;
+}
+
+int ppe_attack_clear_stat(ppe_attack_t *t) {
+    if (!t) return PPE_EINVAL;
+    ATKCHK(t, hipSetDevice(t->ctx->device));
+    ppe_atk_kargs a;
+    std::memset(&a, 0, sizeof a);
+    a.st = t->d_st;
+    a.slots = t->d_slots;
+    a.nslots = t->ctx->max_grid;
+    a.op = PPE_ATK_K_CLEAR;
+    ATKCHK(t, ppe_launch_attack_ctl(&a, t->stream));
+    return PPE_OK;
+}
+
+const char *ppe_attack_last_error(ppe_attack_t *t) { return t ? t->err : "null attack object"; }
+
 int ppe_timing_enable(ppe_ctx_t *c, int on) {
     if (!c) return PPE_EINVAL;
     c->timing = on != 0;
@@ -1694,6 +1973,8 @@ int ppe_classify_flow(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *o
     // PortScan_Detect runs on flow misses only (flow.c:196-215), and whether a packet misses depends on the verdicts
     // of the packets before it: not built
     if (c->ps) return fail(c, PPE_ENOTSUP, "ppe_classify_flow with a port-scan table attached is not supported");
+    // the monitors are built for the stateless kernels only (syncount_accum counts flow creations, FlowAdd)
+    if (c->atk) return fail(c, PPE_ENOTSUP, "ppe_classify_flow with attack monitors attached is not supported");
     int rc = check_batch(c, in, cfg);
     if (rc != PPE_OK || in->n == 0) return rc;
     FlowTable &t = *c->flow;

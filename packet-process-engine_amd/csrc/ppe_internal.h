@@ -184,10 +184,65 @@ struct ppe_kargs {
        attached and enabled (the PSC kernels, csrc/ppe_kernels_portscan.hip): `psmask`, the drop masks the pre-pass wrote,
        one 64-bit word per tile, batch b's at word ppe_bdesc.flags >> PPE_BD_PSOFF_SHIFT; NULL: the kernels without the
        detector.  The two never meet, so they share the bytes: the argument block keeps its size and every offset */
+    /* Stateless launches of a context with attack monitors attached (the ATK kernels, csrc/ppe_kernels_attack*.hip):
+       the fields behind psmask, in the same shared bytes (atk_st NULL: the kernels without the monitors) */
     union {
         struct ppe_flowdev flow;
-        const unsigned long long *psmask;
+        struct {
+            const unsigned long long *psmask;
+            unsigned long long *atk_st;          /* the object's device state (PPE_ATK_*), word 0 the decision word */
+            unsigned long long *atk_slots;       /* [grid][PPE_ATK_SLOT_WORDS]: the workgroups' own count slots */
+            const uint8_t *const *atk_ports;     /* device table: batch k's port bytes, or NULL; NULL: port 0 */
+            uint64_t atk_now;                    /* ppe_attack_clock: OCT_TIME_SECONDS_SINCE1970 */
+            uint32_t atk_hold;                   /* flood_hold_time */
+            uint32_t atk_nports;                 /* entries of atk_ports */
+            uint32_t atk_pbase;                  /* the call's batch index of this launch's batch 0 */
+        };
     };
+};
+
+/* ---- attack monitors (csrc/ppe_attack.hip, the ATK classify kernels; dataplane/src/attack/dp_attack.c) ----
+ * Counts: every classify workgroup adds its per-port accumulator counts and drop totals into a slot of its own
+ * (PPE_ATK_SLOT_WORDS u64: [3 port + class] udp / syn / syncount accum, [12 + t] the drop totals), as the packet
+ * counters do (cslots): no word is shared between workgroups.  The tick kernel folds the slots into the state and
+ * zeroes them; ppe_attack_info adds what they hold.
+ * Device state: u64 words.  [PPE_ATK_WORD] the decision word: port p's six bits at 6 p; [PPE_ATK_TOTALS + 0..3] the
+ * land / udp-flood / syn-flood / syncount drop totals; port p's words at PPE_ATK_PORT0 + PPE_ATK_PORT_STRIDE p. */
+#define PPE_ATK_LAND 1u        /* pd.land == 1 && pd.drop_pack == 1 */
+#define PPE_ATK_UDP_DROP 2u    /* td.flood_udp == 1 && td.drop_pack == 1 && (hold || udppps > udp_speed) */
+#define PPE_ATK_UDP_ARM 4u     /* UDP_DROP and no hold: the first dropped packet sets the hold */
+#define PPE_ATK_SYN_DROP 8u
+#define PPE_ATK_SYN_ARM 16u
+#define PPE_ATK_SYNCOUNT 32u   /* syncount > td.syn_count && td.drop_pack == 1 */
+enum { PPE_ATK_WORD = 0, PPE_ATK_TOTALS = 4, PPE_ATK_PORT0 = 8, PPE_ATK_PORT_STRIDE = 16,
+       /* a port's words: the ten attack_info fields, then the rule reduced to what the monitors read */
+       PPE_ATK_UDPPPS = 0, PPE_ATK_UDP_ACCUM, PPE_ATK_SYNPPS, PPE_ATK_SYN_ACCUM, PPE_ATK_SYNCNT, PPE_ATK_SYNCNT_ACCUM,
+       PPE_ATK_SYN_HOLD, PPE_ATK_SYN_HOLD_TIME, PPE_ATK_UDP_HOLD, PPE_ATK_UDP_HOLD_TIME,
+       PPE_ATK_RULE_EN /* PPE_ATK_EN_* */, PPE_ATK_UDP_SPEED, PPE_ATK_SYN_SPEED, PPE_ATK_SYN_COUNT,
+       PPE_ATK_WORDS = 8 + 16 * 4 };
+#define PPE_ATK_EN_LAND 1u     /* pd.land == 1 && pd.drop_pack == 1 */
+#define PPE_ATK_EN_UDP 2u      /* td.flood_udp == 1 && td.drop_pack == 1 */
+#define PPE_ATK_EN_SYN 4u      /* td.flood_syn == 1 && td.drop_pack == 1 */
+#define PPE_ATK_EN_DROP 8u     /* td.drop_pack == 1 */
+/* the bins (status 29-31, unused, | port << 5) that hold a workgroup's per-port udp_accum / syn_accum /
+ * syncount_accum counts until its flush */
+#define PPE_ATK_BIN_UDP 29u
+#define PPE_ATK_BIN_SYN 30u
+#define PPE_ATK_BIN_SYNCNT 31u
+/* Dec.flags bits that carry the packet's input port to finish() (above the StreamTcp bits 16-21) */
+#define PPE_ATK_PORT_SHIFT 22u
+/* and, until the count that follows decode(), the accumulator it counts in: 0 none, 1 udp_accum, 2 syn_accum */
+#define PPE_ATK_CLS_SHIFT 24u
+#define PPE_ATK_SLOT_WORDS 16u
+#define PPE_ATK_CTL_BLOCK 1024
+enum { PPE_ATK_K_SET = 0, PPE_ATK_K_TICK = 1, PPE_ATK_K_CLEAR = 2 };
+struct ppe_atk_kargs {
+    unsigned long long *st;
+    unsigned long long *slots;                   /* [nslots][PPE_ATK_SLOT_WORDS] */
+    uint32_t nslots, pad0;
+    uint64_t now;                                /* tick */
+    uint32_t rule[4][4];                         /* set: EN bits, udp_speed, syn_speed, syn_count per port */
+    uint32_t op, pad;
 };
 
 /* ---- port-scan detector (csrc/ppe_portscan.hip; dataplane/src/attack/dp_portscan.c) ----
@@ -231,6 +286,10 @@ struct ppe_ps_kargs {
     /* rebuild */
     unsigned long long *dkeys, *drecs;
     uint32_t dmask, age;
+    /* attack monitors attached as well: a packet they drop never reaches PortScan_Detect (the find kernel evaluates
+       the classify kernel's predicate from the same decision word); atk_st NULL: none */
+    const unsigned long long *atk_st;
+    const uint8_t *atk_ports;     /* the batch's port bytes or NULL */
 };
 enum { PPE_PS_K_FIND = 0, PPE_PS_K_CREATORS, PPE_PS_K_SCAN, PPE_PS_K_GRANT, PPE_PS_K_KEYS, PPE_PS_K_SORT_LDS,
        PPE_PS_K_SORT_MERGE_LDS, PPE_PS_K_SORT_GLOBAL, PPE_PS_K_HEADS, PPE_PS_K_MEMBERS, PPE_PS_K_WALK, PPE_PS_K_MASK,
@@ -329,6 +388,11 @@ uint32_t ppe_pick_groups(uint32_t nbatch, uint32_t max_groups);
 /* 1: the launch takes the kernels with the port-scan drop mask (PSC): a stateless launch of a context with a table
  * attached whose detector is enabled (portscan_able == 1, dp_portscan.c:238) */
 uint32_t ppe_pick_portscan(int flow, int attached, uint32_t able);
+/* 1: the launch takes the kernels with the attack monitors (ATK): a stateless launch of a context with an object
+ * attached (ppe_attack_attach), and no other launch */
+uint32_t ppe_pick_attack(int flow, int attached);
+/* the monitors' set / tick / clear kernel (csrc/ppe_attack.hip), stream-ordered.  Returns hipError_t */
+int ppe_launch_attack_ctl(const struct ppe_atk_kargs *a, void *stream);
 /* one kernel of the port-scan pre-pass (csrc/ppe_portscan.hip), grid sized from the arguments.  Returns hipError_t */
 int ppe_launch_portscan(int kind, const struct ppe_ps_kargs *a, void *stream);
 

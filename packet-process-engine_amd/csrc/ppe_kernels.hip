@@ -6,6 +6,9 @@
  *   1. load the first 52 B of the header window (3 × 16-B loads + 1 dword) and the wire length;
  *   2. decode Ethernet → [VLAN] → IPv4 → UDP|TCP exactly as the reference dataplane (big-endian field values,
  *      the reference's check order and uint16/uint8 arithmetic — citations inline);
+ *   2b. with attack monitors attached (ppe_attack_attach; the ATK instantiations, csrc/ppe_kernels_attack*.hip): the
+ *      land / SYN-flood / UDP-flood verdicts inside decode(), from one decision word per launch, and the per-port
+ *      accumulators in spare counter bins, flushed once per workgroup;
  *   3. flow_hashfn (TluHash ×3, dataplane/src/flow/tluhash.h:7-35);
  *   4. on the flow-miss path: syn_check, then the ACL decision-tree walk (image v3, ppe_image.h: one LDS round trip
  *      and four VALU per level, the classifier staged in LDS when it fits) and the leaf's rule check;
@@ -281,10 +284,15 @@ static_assert(PPE_F_VLAN == 1u && PPE_F_L4 == 2u && PPE_F_TCP == 4u, "bin key la
 // PSC (kernels with the port-scan drop mask): status 24 is PortScan_Detect's drop, before the ACL (flow.c:216-230): the
 // RX_OK chain of a packet that reached the flow engine, STAT_FLOW_PROC_FAIL (:281-282) and OUT_DROP; no ACL_*, no
 // FLOW_PROC_OK (attstat.portscan_drop itself is the table's counter, ppe_portscan_info_t.drop)
-template <bool PSC = false>
+// ATK (kernels with the attack monitors): statuses 25-28 dropped inside DecodeIPV4 / DecodeTCP, after STAT_IPV4_RECV_OK
+// and before any UDP / TCP / flow counter (decode-ipv4.c:141-149, decode-tcp.c:162-173), then output_drop_proc
+template <bool PSC = false, bool ATK = false>
 __device__ __forceinline__ uint32_t bin_counters(uint32_t key, uint64_t act_table) {
     const uint32_t st = key & 31u;
     const bool vl = (key >> 5) & 1u, l4 = (key >> 6) & 1u, tcp = (key >> 7) & 1u;
+    if (ATK && st >= PPE_ST_ATTACK_LAND && st <= PPE_ST_ATTACK_UDPFLOOD)
+        return CB(PPE_C_PKTS) | CB(PPE_C_L2_RX_OK) | (vl ? CB(PPE_C_VLAN_RX_OK) : 0u) | CB(PPE_C_IPV4_RX_OK) |
+               CB(PPE_C_OUT_DROP);
     if (PSC && st == PPE_ST_PORTSCAN_DROP)
         return CB(PPE_C_PKTS) | CB(PPE_C_L2_RX_OK) | (vl ? CB(PPE_C_VLAN_RX_OK) : 0u) | CB(PPE_C_IPV4_RX_OK) |
                (tcp ? CB(PPE_C_TCP_RX_OK) : CB(PPE_C_UDP_RX_OK)) | CB(PPE_C_FLOW_PROC_FAIL) | CB(PPE_C_OUT_DROP);
@@ -339,6 +347,12 @@ __device__ __forceinline__ __attribute__((unused)) uint32_t stream_tcp_none(uint
 #define PPE_STREAM_ST_END 24u  // statuses [PPE_ST_STREAM_RST_NO_SESSION, this) are StreamTcp's drop reasons
 static_assert(PPE_ST_PORTSCAN_DROP == PPE_STREAM_BIN0 && (PPE_F_L4 << 5) > PPE_STREAM_BIN0 + 3u,
               "a port-scan drop's bin (status 24, PPE_F_L4 set: key >= 64) stays clear of the stream bins 24..27");
+// the attack monitors' drops: 25-27 always carry PPE_F_TCP (key >= 128), 28 carries at most PPE_F_VLAN (key 28 or 60);
+// their per-port accumulator bins are status 29-31 with the port in the flag bits (keys 29..127): none is 24..27
+static_assert(PPE_ST_ATTACK_LAND == PPE_STREAM_BIN0 + 1u && PPE_ST_ATTACK_SYNCOUNT == PPE_STREAM_BIN0 + 3u &&
+                  (PPE_F_TCP << 5) > PPE_STREAM_BIN0 + 3u && PPE_ST_ATTACK_UDPFLOOD > PPE_STREAM_BIN0 + 3u &&
+                  PPE_ST__ALL == PPE_ATK_BIN_UDP && PPE_ATK_BIN_SYNCNT == 31u,
+              "the attack monitors' bins stay clear of the stream bins 24..27 and of every status");
 
 // Decode of one packet, straight-line: every check of the reference is evaluated, then the terminal status is
 // chosen by applying the checks in REVERSE order of the reference's control flow, so the first failing check
@@ -347,9 +361,13 @@ static_assert(PPE_ST_PORTSCAN_DROP == PPE_STREAM_BIN0 && (PPE_F_L4 << 5) > PPE_S
 // of the n-packet batch decodes the last packet's window, and must read that packet's row).
 // TUP (kernels that may write the tuple output): a fragment's sport / dport / paylen carry what DecodeIPV4 records
 // for Defrag instead (decode-ipv4.c:106-109): ip_id, the fragment offset in bytes and frag_len (ppe_hip.h tuple).
-template <bool TUP = true>
+// ATK (kernels with the attack monitors): atk = the packet's input port << 6 | its port's six decision bits
+// (PPE_ATK_*).  The UDP monitor sits before DecodeUDP (decode-ipv4.c:141-149), so its drop outranks every UDP check;
+// the land / SYN monitors sit behind DecodeTCP's three length checks (decode-tcp.c:162-173), ahead of syn_check.
+template <bool TUP = true, bool ATK = false>
 __device__ __forceinline__ Dec decode(const uint32_t (&w)[13], uint32_t len32, const uint8_t *hdr, uint32_t p,
-                                      uint32_t n, uint32_t stride, uint32_t syn_check, uint32_t stm = 0u) {
+                                      uint32_t n, uint32_t stride, uint32_t syn_check, uint32_t stm = 0u,
+                                      uint32_t atk = 0u) {
     Dec k;
     const uint32_t len = len32 & 0xffffu;  // Decode passes (uint16_t)pkt_totallen, decode.c:22
     // ---- Ethernet: dataplane/src/decode/decode-ethernet.c:23-115 ----
@@ -415,6 +433,23 @@ __device__ __forceinline__ Dec decode(const uint32_t (&w)[13], uint32_t len32, c
     uint32_t st_udp = l4len != x ? (uint32_t)PPE_ST_UDP_LEN_ERR : ST_ACL;  // :26-36
     st_udp = win_short ? (uint32_t)PPE_ST_WINDOW_PUNT : st_udp;
     st_udp = l4len < 8u ? (uint32_t)PPE_ST_UDP_HEADER_ERR : st_udp;  // :18-22
+    bool atk_udp = false, atk_syn = false, atk_tcp_drop = false;  // ATK: counted in udp_accum / syn_accum; 25-27
+    if constexpr (ATK) {
+        // DP_Attack_UdpPacketMonitor (dp_attack.c:582-634): every UDP packet DecodeIPV4 dispatches, whatever its UDP
+        // header (a window punt comes back with a wider window: not judged, not counted)
+        atk_udp = l4_in & is_udp & (st_udp != PPE_ST_WINDOW_PUNT);
+        st_udp = (atk_udp & ((atk & PPE_ATK_UDP_DROP) != 0u)) ? (uint32_t)PPE_ST_ATTACK_UDPFLOOD : st_udp;
+        // DP_Land_Attack_Monitor, then DP_Attack_SynPacketMonitor (dp_attack.c:464-484, 637-688): a SYN that passed the
+        // length checks (st_tcp still ST_ACL: with SYN set, syn_check has not touched it); a land drop is not counted
+        const bool synj = l4_in & is_tcp & syn & (st_tcp == ST_ACL);
+        const bool land = synj & ((atk & PPE_ATK_LAND) != 0u) & (sip == dip);
+        atk_syn = synj & !land;
+        uint32_t sd = (atk & PPE_ATK_SYNCOUNT) ? (uint32_t)PPE_ST_ATTACK_SYNCOUNT : st_tcp;   // :673-685
+        sd = (atk & PPE_ATK_SYN_DROP) ? (uint32_t)PPE_ST_ATTACK_SYNFLOOD : sd;                 // :644-670
+        sd = land ? (uint32_t)PPE_ST_ATTACK_LAND : sd;
+        st_tcp = synj ? sd : st_tcp;
+        atk_tcp_drop = synj & (sd != ST_ACL);
+    }
     uint32_t st = is_tcp ? st_tcp : (is_udp ? st_udp : (uint32_t)PPE_ST_IPV4_UNSUPPORT);  // decode-ipv4.c:233-243
     st = frag ? ((((l3len - hlen) & 0xffffu) == 0u) ? (uint32_t)PPE_ST_FRAG_LEN_ERR : (uint32_t)PPE_ST_FRAG) : st;
     st = ((iplen < hlen) | (l3len < iplen)) ? (uint32_t)PPE_ST_IPV4_LEN_ERR : st;  // decode-ipv4.c:50-60
@@ -438,6 +473,12 @@ __device__ __forceinline__ Dec decode(const uint32_t (&w)[13], uint32_t len32, c
     k.flags = ((l2_ok & is_vl & (vlen >= 4u)) ? PPE_F_VLAN : 0u) | (l4_ok ? PPE_F_L4 : 0u) |
               ((l4_ok & is_tcp) ? PPE_F_TCP : 0u) | ((l4_ok & is_tcp & syn) ? PPE_F_SYN : 0u) |
               ((ip_ok & frag) ? PPE_F_FRAG : 0u);
+    if constexpr (ATK) {
+        // a land / SYN-monitor drop shows the SYN it judged; the port rides to finish() for syncount_accum; the
+        // accumulator bin only counts when the outer checks did not stop the packet first (l4_in says so)
+        k.flags |= (atk_tcp_drop ? (PPE_F_TCP | PPE_F_SYN) : 0u) | ((atk >> 6) << PPE_ATK_PORT_SHIFT) |
+                   ((atk_udp ? 1u : (atk_syn ? 2u : 0u)) << PPE_ATK_CLS_SHIFT);
+    }
     if (stm) {  // wave-uniform (kernel argument): the flag bits StreamTcp looks at, for finish()
         const uint32_t F = (x >> 8) & 0x17u;  // TH_FIN 0x01, TH_SYN 0x02, TH_RST 0x04, TH_ACK 0x10
         k.flags |= (F | ((((F & 0x10u) == 0u) & (ackw != 0u)) ? PPE_SF_BROKEN_ACK : 0u)) << PPE_SF_SHIFT;
@@ -1040,7 +1081,7 @@ __device__ __forceinline__ void stage_image(const uint32_t *img, uint32_t *lds, 
 // (NST: statuses in the table; the kernels without the port-scan mask keep the 24-entry constant)
 template <uint32_t NST = PPE_ST__COUNT>
 __device__ __forceinline__ uint64_t make_act_table(uint32_t unsup_fw) {
-    static_assert(NST <= PPE_ST__END && 2u * NST <= 64u, "2 bits per status");
+    static_assert(NST <= PPE_ST__ALL && 2u * NST <= 64u, "2 bits per status");
     uint64_t t = 0;
 #pragma unroll
     for (uint32_t st = 0; st < NST; ++st) {
@@ -1323,12 +1364,39 @@ __device__ __forceinline__ uint32_t flow_find_claim(const ppe_flowdev &f, const 
 #ifndef PPE_CUT_SPLIT_WAVES  // the same for split images (entries from L2)
 #define PPE_CUT_SPLIT_WAVES PPE_WAVES_PER_EU
 #endif
+// What an ATK kernel keeps per wave: the launch's decision word and the current batch's port bytes (NULL: port 0)
+struct AtkWave {
+    uint32_t word;
+    const uint8_t *pb;
+    __device__ __forceinline__ void batch(const ppe_kargs &a, uint32_t bi) {
+        const uint32_t k = a.atk_pbase + bi;
+        pb = (a.atk_ports && k < a.atk_nports) ? a.atk_ports[k] : nullptr;
+    }
+    // packet p of an n-packet batch: its input port << 6 | the port's six decision bits, for decode()
+    __device__ __forceinline__ uint32_t bits(uint32_t p, uint32_t n) const {
+        uint32_t port = 0;
+        if (pb && p < n) port = (uint32_t)pb[p] & 3u;
+        return ((word >> (6u * port)) & 63u) | (port << 6);
+    }
+};
+struct AtkNone {};
+template <bool ATK> struct AtkSel { typedef AtkWave type; };
+template <> struct AtkSel<false> { typedef AtkNone type; };
+// the packet's udp_accum / syn_accum count, from the class and port bits decode() left in its flags
+__device__ __forceinline__ void atk_count(uint32_t *bins, uint32_t flags) {
+    const uint32_t cls = (flags >> PPE_ATK_CLS_SHIFT) & 3u;
+    if (cls) atomicAdd(&bins[PPE_ATK_BIN_UDP - 1u + cls + (((flags >> PPE_ATK_PORT_SHIFT) & 3u) << 5)], 1u);
+}
+
 // STM: StreamTcp's first-packet verdict (ppe_stream_tcp_set tracking on; stateless kernels only).  A template
 // parameter, not a run-time branch: the 64-VGPR kernels have no register to spare (as a uniform branch the check
 // cost C1's kernel 2 spilled VGPRs with tracking off), so with tracking off the kernels contain none of it.
 // PSC: the port-scan detector's drop mask (a table with able = 1 attached, ppe_portscan_attach; stateless kernels only;
 // csrc/ppe_kernels_portscan.hip), a template parameter for the same reason; combines with STM.
-template <int MODE, int PF, int BLOCK, bool FLOW, bool PART = false, bool STM = false, bool PSC = false>
+// ATK: the attack monitors (an object attached, ppe_attack_attach; stateless kernels only;
+// csrc/ppe_kernels_attack*.hip), a template parameter for the same reason; combines with STM and PSC.
+template <int MODE, int PF, int BLOCK, bool FLOW, bool PART = false, bool STM = false, bool PSC = false,
+          bool ATK = false>
 __global__ __launch_bounds__(BLOCK, (PF == PF_MULTI && !FLOW) ? PPE_MT_WAVES
                                     : FLOW                                       ? PPE_FLOW_WAVES
                                     : (PF == PF_CUT && MODE == IMG_LDS)          ? PPE_CUT_LDS_WAVES
@@ -1345,6 +1413,7 @@ void ppe_classify_kernel(ppe_kargs a) {
     constexpr bool KEYS = MT == 1 && !CUT;  // node walks: per-wave key slots in LDS
     static_assert(!(STM && FLOW), "stream tracking: stateless kernels only");
     static_assert(!(PSC && FLOW), "port-scan mask: stateless kernels only");
+    static_assert(!(ATK && FLOW), "attack monitors: stateless kernels only");
     const uint32_t stm = STM ? a.stream : 0u;
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     using L = Lds<BLOCK, KEYS, FLOW ? 4u * PPE_UPD_OWNERS * (1u + (PPE_UPD_LDS ? PPE_UPD_CAP : 0u)) : 0u>;
@@ -1382,6 +1451,13 @@ void ppe_classify_kernel(ppe_kargs a) {
         return __builtin_bit_cast(ppe_bdesc, d);
     };
     ppe_bdesc B = bdesc(wave_live ? grp : 0u);
+    // ATK: the decision word (one uniform load per launch: nothing changes it between two ticks) and the current
+    // batch's port bytes, looked up wherever B changes.  Without ATK the object is empty and nothing below names it
+    typename AtkSel<ATK>::type atk;
+    if constexpr (ATK) {
+        atk.word = (uint32_t)a.atk_st[PPE_ATK_WORD];
+        atk.batch(a, wave_live ? grp : 0u);
+    }
     // current tile's window: bytes 0..51 (w[0..12]) and the wire length.  Clamped (unconditional) loads: a lane past
     // the end of the batch re-reads the last packet.  Byte offsets are 32-bit (the engine keeps n * stride < 2^31).
     uint4 q0, q1, q2;
@@ -1412,7 +1488,7 @@ void ppe_classify_kernel(ppe_kargs a) {
                         a.cut, a.cut_slc, a.cut_gbase, a.cut_fp, a.cut_ent, a.cut_epl, a.cut_div, a.cut_idrel,
                         a.cut_gbase_lds, a.cut_fp_lds, a.cut_ent_lds};
 
-    const uint64_t act_table = make_act_table<PSC ? PPE_ST__END : PPE_ST__COUNT>(a.unsup_fw);
+    const uint64_t act_table = make_act_table<ATK ? PPE_ST__ALL : PSC ? PPE_ST__END : PPE_ST__COUNT>(a.unsup_fw);
     // (this batch's creator counter was zeroed by the previous batch's finalize launch)
     if (FLOW && blockIdx.x == 0 && tid == 0) {
         // the table state after the previous batches, for the host's bounds (zero-copy, no stream stall); LIVE is
@@ -1445,6 +1521,13 @@ void ppe_classify_kernel(ppe_kargs a) {
     auto finish = [&](uint32_t tile, uint32_t p, bool valid, const Dec &k, uint32_t fh, int32_t hit, bool pend,
                       uint32_t sfw) {
         uint32_t st = k.st;
+        if constexpr (ATK) {
+            // DP_Attack_SynCountMonitor in FlowAdd (flow.c:151-154): a TCP SYN the ACL forwarded, after the port-scan
+            // mask and before StreamTcp's verdict (flow.c:243 precedes :311)
+            if (!(PPE_ABLATE & 2) && valid && st == PPE_ST_ACL_FW &&
+                (k.flags & (PPE_F_TCP | PPE_F_SYN)) == (PPE_F_TCP | PPE_F_SYN))
+                atomicAdd(&bins[PPE_ATK_BIN_SYNCNT + (((sfw >> PPE_ATK_PORT_SHIFT) & 3u) << 5)], 1u);
+        }
         if constexpr (STM) {
             // StreamTcp (flow.c:311-320) for the TCP packets the ACL forwarded, each the first of its flow: the
             // counters of stream-tcp.c:2989-3003 (wave ballots, one LDS add per tile and counter), then the verdict
@@ -1531,7 +1614,11 @@ void ppe_classify_kernel(ppe_kargs a) {
         const uint32_t p = (tile << 6) + lane;
         const bool valid = p < B.n;
         if (!(PPE_ABLATE & 2) && valid) rx_bytes += wlen;
-        Dec k = decode<!PART>(w, wlen, B.hdr, p, B.n, B.stride, a.syn_check, stm);
+        uint32_t ab = 0;
+        if constexpr (ATK) ab = atk.bits(p, B.n);
+        Dec k = decode<!PART, ATK>(w, wlen, B.hdr, p, B.n, B.stride, a.syn_check, stm, ab);
+        if constexpr (ATK)  // udp_accum / syn_accum of the packet's port
+            if (!(PPE_ABLATE & 2) && valid) atk_count(bins, k.flags);
 
         uint32_t fh = 0;
         int32_t hit = -1;
@@ -1590,7 +1677,11 @@ void ppe_classify_kernel(ppe_kargs a) {
             if (p < B.n) rx_bytes += rl[t];
             const uint32_t w[13] = {r0[t].x, r0[t].y, r0[t].z, r0[t].w, r1[t].x, r1[t].y, r1[t].z, r1[t].w,
                                     r2[t].x, r2[t].y, r2[t].z, r2[t].w, r3[t]};
-            Dec d = decode<!PART>(w, rl[t], B.hdr, p, B.n, B.stride, a.syn_check, stm);
+            uint32_t ab = 0;
+            if constexpr (ATK) ab = atk.bits(p, B.n);
+            Dec d = decode<!PART, ATK>(w, rl[t], B.hdr, p, B.n, B.stride, a.syn_check, stm, ab);
+            if constexpr (ATK)
+                if (!(PPE_ABLATE & 2) && p < B.n) atk_count(bins, d.flags);
             if ((PPE_ABLATE & 1) && d.st == ST_ACL) {
                 d.st = PPE_ST_ACL_FW;
                 d.flags |= PPE_F_ACL;
@@ -1668,6 +1759,7 @@ void ppe_classify_kernel(ppe_kargs a) {
             live = bi < a.nbatch;
             if (live) B = bdesc(bi);
         }
+        if constexpr (ATK) atk.batch(a, bi);
         if (live) load_round(B.hdr, B.len, B.n, B.stride, t0);
         while (live) {
             const uint32_t ntiles = (B.n + 63u) >> 6;
@@ -1719,6 +1811,8 @@ void ppe_classify_kernel(ppe_kargs a) {
                 mt_finish(t0 + t, key[t], kpay[t], kopt[t], need[t], hit[t], drop[t]);
             }
             if (nlive && nbi != bi) B = bdesc(nbi);
+            if constexpr (ATK)
+                if (nlive && nbi != bi) atk.batch(a, nbi);
             bi = nbi;
             t0 = nt0;
             live = nlive;
@@ -1727,6 +1821,8 @@ void ppe_classify_kernel(ppe_kargs a) {
         // PF_MULTI: wave w takes tiles [MT w, MT w + MT), then + MT W, ...; all MT windows are requested together
         for (uint32_t bi = grp; wave_live && bi < a.nbatch; bi += ngroups) {
             if (bi != grp) B = bdesc(bi);
+            if constexpr (ATK)
+                if (bi != grp) atk.batch(a, bi);
             const uint32_t ntiles = (B.n + 63u) >> 6;
             for (uint32_t t0 = wtile * MT; t0 < ntiles; t0 += stride_waves * MT) {
                 uint4 r0[MT], r1[MT], r2[MT];
@@ -1778,6 +1874,8 @@ void ppe_classify_kernel(ppe_kargs a) {
     } else
     for (uint32_t bi = grp; wave_live && bi < a.nbatch; bi += ngroups) {
         if (bi != grp) B = bdesc(bi);
+        if constexpr (ATK)
+            if (bi != grp) atk.batch(a, bi);
         const uint32_t ntiles = (B.n + 63u) >> 6;
         for (uint32_t tile = wtile; tile < ntiles; tile += stride_waves) {
             if (!have) load_tile(tile);
@@ -1796,8 +1894,40 @@ void ppe_classify_kernel(ppe_kargs a) {
     for (uint32_t b = tid; b < PPE_NBINS; b += BLOCK) {  // expand the bins into counter increments
         const uint32_t c = bins[b];
         if (c) {
+            if constexpr (ATK) {
+                const uint32_t st = b & 31u, port = (b >> 5) & 3u;
+                unsigned long long *ps = a.atk_st + PPE_ATK_PORT0 + PPE_ATK_PORT_STRIDE * port;
+                unsigned long long *slot = a.atk_slots + (size_t)blockIdx.x * PPE_ATK_SLOT_WORDS;
+                if (st >= PPE_ATK_BIN_UDP) {
+                    // this workgroup's share of a port's udp_accum / syn_accum / syncount_accum: one add per non-empty
+                    // bin into the workgroup's own slot (one word shared by every workgroup cost 7 us per 1M
+                    // packets: the adds of 2,048 workgroups queue behind each other).  Then the hold (dp_attack.c:618-620,
+                    // :664-666): the port's ARM bit says every packet just counted was dropped by the speed branch
+                    // with no hold set; 0 -> 1 once, the winner stores the time; a workgroup that reads it set leaves
+                    // it.  No verdict reads the flag before the next tick, so racing workgroups are harmless
+                    const bool udp = st == PPE_ATK_BIN_UDP;
+                    __hip_atomic_fetch_add(&slot[3u * port + (st - PPE_ATK_BIN_UDP)], (unsigned long long)c,
+                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    const uint32_t arm = udp ? PPE_ATK_UDP_ARM : st == PPE_ATK_BIN_SYN ? PPE_ATK_SYN_ARM : 0u;
+                    if (((uint32_t)a.atk_st[PPE_ATK_WORD] >> (6u * port)) & arm) {
+                        unsigned long long *hold = &ps[udp ? PPE_ATK_UDP_HOLD : PPE_ATK_SYN_HOLD];
+                        if (__hip_atomic_load(hold, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0ull &&
+                            atomicCAS(hold, 0ull, 1ull) == 0ull)
+                            __hip_atomic_store(hold + 1, (unsigned long long)(a.atk_now + a.atk_hold), __ATOMIC_RELAXED,
+                                               __HIP_MEMORY_SCOPE_AGENT);
+                    }
+                    continue;
+                }
+                if (st >= PPE_ST_ATTACK_LAND && b > PPE_STREAM_BIN0 + 3u) {  // attstat.land / synspeed / syncount / udpspeed
+                    const uint32_t t = st == PPE_ST_ATTACK_LAND ? 0u : st == PPE_ST_ATTACK_UDPFLOOD ? 1u
+                                       : st == PPE_ST_ATTACK_SYNFLOOD ? 2u : 3u;
+                    __hip_atomic_fetch_add(&slot[12u + t], (unsigned long long)c, __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_AGENT);
+                }
+            }
             if (STM && (b & 31u) >= PPE_ST_STREAM_RST_NO_SESSION &&
-                !(PSC && b >= 32u && (b & 31u) == PPE_ST_PORTSCAN_DROP)) {
+                !(PSC && b >= 32u && (b & 31u) == PPE_ST_PORTSCAN_DROP) &&
+                !(ATK && (b & 31u) >= PPE_ST_ATTACK_LAND && b > PPE_STREAM_BIN0 + 3u)) {
                 // StreamTcp tracking: this workgroup's counts into its own stream counter slot (uncontended), one add
                 // per non-empty bin: the count-first accumulators, and each drop's reason (its status bins)
                 const uint32_t st = b & 31u;
@@ -1809,7 +1939,7 @@ void ppe_classify_kernel(ppe_kargs a) {
                                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if (st >= PPE_STREAM_ST_END) continue;
             }
-            for (uint32_t cb = bin_counters<PSC>(b, act_table); cb; cb &= cb - 1u) atomicAdd(&lcnt[__builtin_ctz(cb)], c);
+            for (uint32_t cb = bin_counters<PSC, ATK>(b, act_table); cb; cb &= cb - 1u) atomicAdd(&lcnt[__builtin_ctz(cb)], c);
         }
     }
     if (FLOW && blockIdx.x < a.flow.upd_wgs) {  // this workgroup's row of bucket counts, for the update kernel
@@ -2473,6 +2603,41 @@ extern "C" int ppe_launch_classify_portscan(
     const hipEvent_t e0 = (hipEvent_t)ev_start, e1 = (hipEvent_t)ev_stop;
     PPE_DISPATCH(launch_psc_t, a, grid, shmem, s, e0, e1);
 }
+#elif defined(PPE_TU_ATTACK)
+// csrc/ppe_kernels_attack*.hip: this file again, exporting only the stateless kernels with the attack monitors (ATK):
+// PPE_TU_ATTACK 1 alone, 2 with StreamTcp's verdict, 3 with the port-scan drop mask, 4 with both
+constexpr bool kAtkStm = PPE_TU_ATTACK == 2 || PPE_TU_ATTACK == 4, kAtkPsc = PPE_TU_ATTACK >= 3;
+template <int M, int P, int B>
+static int launch_atk_t(const ppe_kargs *a, uint32_t grid, size_t shmem, hipStream_t s, hipEvent_t e0,
+                        hipEvent_t e1) {
+    if constexpr (P != PF_NONE) {  // (the throughput-layout variants exist for the same fetch modes as without ATK)
+        if (a->part_layout)
+            hipExtLaunchKernelGGL((ppe_classify_kernel<M, P, B, false, true, kAtkStm, kAtkPsc, true>), dim3(grid),
+                                  dim3(B), shmem, s, e0, e1, 0, *a);
+        else
+            hipExtLaunchKernelGGL((ppe_classify_kernel<M, P, B, false, false, kAtkStm, kAtkPsc, true>), dim3(grid),
+                                  dim3(B), shmem, s, e0, e1, 0, *a);
+    } else {
+        hipExtLaunchKernelGGL((ppe_classify_kernel<M, P, B, false, false, kAtkStm, kAtkPsc, true>), dim3(grid), dim3(B),
+                              shmem, s, e0, e1, 0, *a);
+    }
+    return (int)hipGetLastError();
+}
+#if PPE_TU_ATTACK == 4
+extern "C" int ppe_launch_classify_attack_portscan_stream(
+#elif PPE_TU_ATTACK == 3
+extern "C" int ppe_launch_classify_attack_portscan(
+#elif PPE_TU_ATTACK == 2
+extern "C" int ppe_launch_classify_attack_stream(
+#else
+extern "C" int ppe_launch_classify_attack(
+#endif
+    const ppe_kargs *a, uint32_t grid, size_t shmem, int mode, int pipe, int block, void *stream, void *ev_start,
+    void *ev_stop) {
+    const hipStream_t s = (hipStream_t)stream;
+    const hipEvent_t e0 = (hipEvent_t)ev_start, e1 = (hipEvent_t)ev_stop;
+    PPE_DISPATCH(launch_atk_t, a, grid, shmem, s, e0, e1);
+}
 #elif defined(PPE_TU_STREAM)
 // csrc/ppe_kernels_stream.hip: this file again, exporting only the stateless kernels with StreamTcp's verdict (STM)
 template <int M, int P, int B>
@@ -2542,6 +2707,10 @@ extern "C" int ppe_launch_classify_portscan(const ppe_kargs *a, uint32_t grid, s
                                             int block, void *stream, void *ev_start, void *ev_stop);
 extern "C" int ppe_launch_classify_portscan_stream(const ppe_kargs *a, uint32_t grid, size_t shmem, int mode, int pipe,
                                                    int block, void *stream, void *ev_start, void *ev_stop);
+typedef int ppe_launch_variant_fn(const ppe_kargs *a, uint32_t grid, size_t shmem, int mode, int pipe, int block,
+                                  void *stream, void *ev_start, void *ev_stop);
+extern "C" ppe_launch_variant_fn ppe_launch_classify_attack, ppe_launch_classify_attack_stream,
+    ppe_launch_classify_attack_portscan, ppe_launch_classify_attack_portscan_stream;
 
 template <int M, int P, int B>
 static int launch_t(const ppe_kargs *a, uint32_t grid, size_t shmem, hipStream_t s, hipEvent_t e0, hipEvent_t e1,
@@ -2593,6 +2762,13 @@ extern "C" int ppe_launch_classify(const ppe_kargs *a, uint32_t grid, int mode, 
     // occupancy and grid), from its own translation unit
     // a port-scan table attached and enabled: the kernels that read the pre-pass's drop mask, with or without StreamTcp
     // (same launch bounds and LDS again)
+    // attack monitors attached: the kernels with them, alone or with either or both of the above (the same again)
+    if (!flow && a->atk_st) {
+        ppe_launch_variant_fn *const f =
+            a->psmask ? (a->stream ? ppe_launch_classify_attack_portscan_stream : ppe_launch_classify_attack_portscan)
+                      : (a->stream ? ppe_launch_classify_attack_stream : ppe_launch_classify_attack);
+        return f(a, grid, shmem, mode, pipe, block, stream, ev_start, ev_stop);
+    }
     if (a->psmask && !flow)
         return (a->stream ? ppe_launch_classify_portscan_stream : ppe_launch_classify_portscan)(
             a, grid, shmem, mode, pipe, block, stream, ev_start, ev_stop);

@@ -78,6 +78,10 @@ __device__ __forceinline__ void ps_flush(unsigned long long *ctl, const uint32_t
                                __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// ATK (attack monitors attached as well; chosen on the host): a packet they drop returns before FlowHandlePacket and
+// never gets here: the classify kernel's own predicate, from the same decision word and port byte.  Without ATK the
+// kernel holds none of it
+template <bool ATK>
 __global__ __launch_bounds__(PS_BLOCK) void ps_find_kernel(ppe_ps_kargs a) {
     __shared__ uint32_t occ;
     if (threadIdx.x == 0) occ = 0;
@@ -88,7 +92,12 @@ __global__ __launch_bounds__(PS_BLOCK) void ps_find_kernel(ppe_ps_kargs a) {
     const uint4 q0 = gld<uint4>(a.hdr, ro), q1 = gld<uint4>(a.hdr, ro + 16u), q2 = gld<uint4>(a.hdr, ro + 32u);
     const uint32_t w12 = gld<uint32_t>(a.hdr, ro + 48u), wlen = gld<uint32_t>(a.len, 4u * pc);
     const uint32_t w[13] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, w12};
-    const Dec k = decode<false>(w, wlen, a.hdr, pc, a.n, a.stride, a.syn_check);
+    uint32_t bits = 0;
+    if constexpr (ATK) {
+        const uint32_t port = a.atk_ports ? (uint32_t)a.atk_ports[pc] & 3u : 0u;
+        bits = (((uint32_t)a.atk_st[PPE_ATK_WORD] >> (6u * port)) & 63u) | (port << 6);
+    }
+    const Dec k = decode<false, ATK>(w, wlen, a.hdr, pc, a.n, a.stride, a.syn_check, 0u, bits);
     // flow.c:204-215: the packet reaches PortScan_Detect iff it would reach DP_Acl_Lookup
     const bool elig = i < a.n && k.st == ST_ACL;
     uint32_t slot = PPE_PS_NOSLOT;
@@ -463,7 +472,10 @@ extern "C" int ppe_launch_portscan(int kind, const ppe_ps_kargs *a, void *stream
     const dim3 b(PS_BLOCK);
     const dim3 gn((a->n + PS_BLOCK - 1) / PS_BLOCK), gp((a->npad + PS_BLOCK - 1) / PS_BLOCK);
     switch (kind) {
-        case PPE_PS_K_FIND: hipLaunchKernelGGL(ps_find_kernel, gn, b, 0, s, *a); break;
+        case PPE_PS_K_FIND:
+            if (a->atk_st) hipLaunchKernelGGL(ps_find_kernel<true>, gn, b, 0, s, *a);
+            else hipLaunchKernelGGL(ps_find_kernel<false>, gn, b, 0, s, *a);
+            break;
         case PPE_PS_K_CREATORS: hipLaunchKernelGGL(ps_creators_kernel, gn, b, 0, s, *a); break;
         case PPE_PS_K_SCAN: hipLaunchKernelGGL(ps_scan_kernel, dim3(1), dim3(1024), 0, s, *a); break;
         case PPE_PS_K_GRANT: hipLaunchKernelGGL(ps_grant_kernel, gn, b, 0, s, *a); break;

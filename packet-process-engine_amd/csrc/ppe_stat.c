@@ -24,6 +24,7 @@
 /* reassembly-table sources (ppe_defrag_info_t), printed 0 without one */
 #define DF(st) (1000 + (st))   /* fragments with Defrag outcome st */
 #define DF_TEARDROP 2000       /* overlaps, while the teardrop monitor is enabled */
+#define ATK(i) (4000 + (i))     /* drop total i of the attack monitors (ppe_attack_info_t: land, udp, syn, syncount), 0 without */
 #define PS_DROP 3000           /* attstat.portscan_drop of a port-scan table (ppe_portscan_info_t), printed 0 without one */
 
 typedef struct {
@@ -74,9 +75,9 @@ static const stat_line_t k_out[] = {{"output_fw", NONE}, {"output_drop", NONE}, 
                                     {"output_unsupport", NONE}};
 static const stat_line_t k_tx[] = {{"port_err", NONE}, {"hw_send_err", NONE}, {"sw_desc_err", NONE},
                                    {"sw_send_err", NONE}, {"send_over", NONE}};
-static const stat_line_t k_att[] = {{"land_drop", NONE}, {"teardrop", DF_TEARDROP}, {"pingdeath", NONE},
-                                    {"ping flood drop", NONE}, {"udp flood drop", NONE}, {"syn flood drop", NONE},
-                                    {"syncount", NONE}, {"portscan_drop", PS_DROP}};
+static const stat_line_t k_att[] = {{"land_drop", ATK(0)}, {"teardrop", DF_TEARDROP}, {"pingdeath", NONE},
+                                    {"ping flood drop", NONE}, {"udp flood drop", ATK(1)}, {"syn flood drop", ATK(2)},
+                                    {"syncount", ATK(3)}, {"portscan_drop", PS_DROP}};
 
 #define SEC(t, a, b) {t, a, (int)(sizeof a / sizeof a[0]), b}
 static const stat_section_t k_sections[] = {
@@ -102,8 +103,13 @@ static void put(out_t *o, const char *fmt, ...) {
 }
 
 static long line_value(const ppe_counters_t *c, const ppe_defrag_info_t *df, int teardrop_monitor,
-                       const ppe_portscan_info_t *ps, int ci) {
+                       const ppe_portscan_info_t *ps, const ppe_attack_info_t *atk, int ci) {
     if (ci == NONE) return 0L;
+    if (ci >= 4000) {
+        if (!atk) return 0L;
+        const uint64_t v[4] = {atk->land_drop, atk->udpflood_drop, atk->synflood_drop, atk->syncount_drop};
+        return (long)v[ci - 4000];
+    }
     if (ci == PS_DROP) return ps ? (long)ps->drop : 0L;
     if (ci == DF_TEARDROP) return df && teardrop_monitor ? (long)df->teardrop : 0L;
     if (ci >= 1000) return df ? (long)df->st[ci - 1000] : 0L;
@@ -121,6 +127,12 @@ int ppe_format_pkt_stat_ex(const ppe_counters_t *c, const ppe_defrag_info_t *df,
 
 int ppe_format_pkt_stat_ps(const ppe_counters_t *c, const ppe_defrag_info_t *df, int teardrop_monitor,
                            const ppe_portscan_info_t *ps_info, char *buf, size_t cap) {
+    return ppe_format_pkt_stat_atk(c, df, teardrop_monitor, ps_info, NULL, buf, cap);
+}
+
+int ppe_format_pkt_stat_atk(const ppe_counters_t *c, const ppe_defrag_info_t *df, int teardrop_monitor,
+                            const ppe_portscan_info_t *ps_info, const ppe_attack_info_t *atk_info, char *buf,
+                            size_t cap) {
     if (!c) return PPE_EINVAL;
     out_t o = {buf, buf ? cap : 0, 0};
     if (buf && cap) buf[0] = 0;
@@ -133,11 +145,55 @@ int ppe_format_pkt_stat_ps(const ppe_counters_t *c, const ppe_defrag_info_t *df,
         put(&o, "----------------\n");
         for (int i = 0; i < sec->n; i++) {
             const int ci = sec->lines[i].counter;
-            put(&o, "%s: %ld\n", sec->lines[i].name, line_value(c, df, teardrop_monitor, ps_info, ci));
+            put(&o, "%s: %ld\n", sec->lines[i].name, line_value(c, df, teardrop_monitor, ps_info, atk_info, ci));
         }
         put(&o, "----------------\n");
         if (sec->blank_after) put(&o, "\n");
     }
+    return (int)o.len;
+}
+
+/* `show attack stat` (dp_show_attack_stat, dp_cmd.c:2394-2529): the rules and the monitor state of the four
+ * interfaces, same format strings (%d for the rule words, %ld for the state) */
+int ppe_format_attack_stat(const ppe_attack_info_t *info, char *buf, size_t cap) {
+    if (!info) return PPE_EINVAL;
+    out_t o = {buf, buf ? cap : 0, 0};
+    if (buf && cap) buf[0] = 0;
+    put(&o, "attack rule:\n");
+    for (int i = 0; i < PPE_ATTACK_PORTS; i++) {
+        const ppe_attack_pd_t *pd = &info->cfg.pd[i];
+        const ppe_attack_td_t *td = &info->cfg.td[i];
+        const ppe_attack_port_t *ai = &info->ai[i];
+        put(&o, "----------------\n");
+        put(&o, "interface %d:\n", i);
+        put(&o, "packet detect:\n");
+        put(&o, "drop_pack: %d\n", (int)pd->drop_pack);
+        put(&o, "land: %d\n", (int)pd->land);
+        put(&o, "teardrop: %d\n", (int)pd->teardrop);
+        put(&o, "pingdeath: %d\n", (int)pd->pingdeath);
+        put(&o, "pingdeath_value: %d\n", (int)pd->pingdeath_value);
+        put(&o, "\n");
+        put(&o, "traffic detect:\n");
+        put(&o, "drop_pack: %d\n", (int)td->drop_pack);
+        put(&o, "flood_ping: %d\n", (int)td->flood_ping);
+        put(&o, "ping_speed: %d\n", (int)td->ping_speed);
+        put(&o, "flood_udp: %d\n", (int)td->flood_udp);
+        put(&o, "udp_speed: %d\n", (int)td->udp_speed);
+        put(&o, "flood_syn: %d\n", (int)td->flood_syn);
+        put(&o, "syn_speed: %d\n", (int)td->syn_speed);
+        put(&o, "syn_count: %d\n", (int)td->syn_count);
+        put(&o, "\n");
+        put(&o, "attack monitor info:\n");
+        put(&o, "pingpps: %ld\n", (long)ai->pingpps);
+        put(&o, "ping_accum: %ld\n", (long)ai->ping_accum);
+        put(&o, "udppps: %ld\n", (long)ai->udppps);
+        put(&o, "udp_accum: %ld\n", (long)ai->udp_accum);
+        put(&o, "synpps: %ld\n", (long)ai->synpps);
+        put(&o, "syn_accum: %ld\n", (long)ai->syn_accum);
+        put(&o, "syncount: %ld\n", (long)ai->syncount);
+        put(&o, "syncount_accum: %ld\n", (long)ai->syncount_accum);
+    }
+    put(&o, "----------------------------\n");
     return (int)o.len;
 }
 

@@ -4,4 +4,4 @@ Plumbing for tests and bench.py only: every classification runs in the HIP kerne
 """
 from . import abi, synth  # noqa: F401
 from .abi import RULE_DTYPE, ST, ST_NAME, COUNTERS, build_image  # noqa: F401
-from .engine import Defrag, Engine, PortScan, PPEError, decode_verdict  # noqa: F401
+from .engine import Attack, Defrag, Engine, PortScan, PPEError, decode_verdict  # noqa: F401

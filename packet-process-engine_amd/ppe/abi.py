@@ -25,8 +25,11 @@ ST = dict(ACL_FW=0, ACL_DROP=1, L2_HEADER_ERR=2, L2_UNSUPPORT=3, VLAN_HEADER_ERR
           STREAM_RST_NO_SESSION=20, STREAM_FIN_NO_SESSION=21, STREAM_MIDSTREAM_ONESIDE_OFF=22,
           STREAM_MIDSTREAM_OFF=23,
           # PortScan_Detect's drop (a table attached with ppe_portscan_attach)
-          PORTSCAN_DROP=24)
-ST_COUNT, ST_END = 24, 25  # PPE_ST__COUNT (statuses without a port-scan table), PPE_ST__END (all of them)
+          PORTSCAN_DROP=24,
+          # the attack monitors' drops (an object attached with ppe_attack_attach)
+          ATTACK_LAND=25, ATTACK_SYNFLOOD=26, ATTACK_SYNCOUNT=27, ATTACK_UDPFLOOD=28)
+ST_COUNT, ST_END = 24, 25  # PPE_ST__COUNT (statuses without a port-scan table), PPE_ST__END (with one)
+ST_ALL = 29                # PPE_ST__ALL (every status, the attack monitors' included)
 ST_NAME = {v: k for k, v in ST.items()}
 # enum ppe_stream_counter (ppe_stream_counters_t.c[])
 STREAM_COUNTERS = ["syn_ack_count", "syn_count", "rst_count", "rst_but_no_session", "fin_but_no_session",
@@ -142,6 +145,65 @@ class PortScanInfo(C.Structure):  # ppe_portscan_info_t
 PORTSCAN_ENTRY_DTYPE = np.dtype([("sip", "<u4"), ("last_dport", "<u4"), ("exception", "<u4"),
                                  ("last_exception", "<u4"), ("last_cycle", "<u8"), ("cycle", "<u8"), ("hold", "<u8")])
 assert PORTSCAN_ENTRY_DTYPE.itemsize == 40
+
+
+ATTACK_PORTS = 4  # PPE_ATTACK_PORTS (OCT_PHY_PORT_MAX)
+
+
+class AttackPd(C.Structure):  # ppe_attack_pd_t (packet_detect)
+    _fields_ = [(k, C.c_uint32) for k in ("drop_pack", "land", "teardrop", "pingdeath", "pingdeath_value")]
+
+
+class AttackTd(C.Structure):  # ppe_attack_td_t (traffic_detect)
+    _fields_ = [(k, C.c_uint32) for k in ("drop_pack", "flood_ping", "ping_speed", "last_ping_flood_time", "flood_udp",
+                                          "udp_speed", "last_udp_flood_time", "flood_syn", "syn_speed",
+                                          "last_syn_flood_time", "syn_count")]
+
+
+class AttackCfg(C.Structure):  # ppe_attack_cfg_t
+    _fields_ = [("pd", AttackPd * ATTACK_PORTS), ("td", AttackTd * ATTACK_PORTS), ("hold_seconds", C.c_uint32),
+                ("pad", C.c_uint32)]
+
+    @classmethod
+    def make(cls, pd=None, td=None, hold_seconds=600):
+        """pd / td: {port: {field: value}}; the fields not given are 0."""
+        c = cls()
+        for p, d in (pd or {}).items():
+            for k, v in d.items():
+                setattr(c.pd[p], k, int(v))
+        for p, d in (td or {}).items():
+            for k, v in d.items():
+                setattr(c.td[p], k, int(v))
+        c.hold_seconds = int(hold_seconds)
+        return c
+
+    def as_dict(self):
+        return {"pd": [{k: getattr(x, k) for k, _ in x._fields_} for x in self.pd],
+                "td": [{k: getattr(x, k) for k, _ in x._fields_} for x in self.td],
+                "hold_seconds": self.hold_seconds}
+
+
+ATTACK_STATE_FIELDS = ("udppps", "udp_accum", "synpps", "syn_accum", "syncount", "syncount_accum", "syn_flood_hold",
+                       "syn_flood_hold_time", "udp_flood_hold", "udp_flood_hold_time")  # the ten this path moves
+ATTACK_TOTALS = ("land_drop", "udpflood_drop", "synflood_drop", "syncount_drop")
+
+
+class AttackPort(C.Structure):  # ppe_attack_port_t (attack_info)
+    _fields_ = [(k, C.c_uint64) for k in ("pingpps", "ping_accum", "udppps", "udp_accum", "synpps", "syn_accum",
+                                          "syncount", "syncount_accum", "ping_flood_hold", "ping_flood_hold_time",
+                                          "syn_flood_hold", "syn_flood_hold_time", "udp_flood_hold",
+                                          "udp_flood_hold_time")]
+
+
+class AttackInfo(C.Structure):  # ppe_attack_info_t
+    _fields_ = [("cfg", AttackCfg), ("ai", AttackPort * ATTACK_PORTS)] + [(k, C.c_uint64) for k in ATTACK_TOTALS] + \
+               [("now_seconds", C.c_uint64)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k in ATTACK_TOTALS + ("now_seconds",)}
+        d["cfg"] = self.cfg.as_dict()
+        d["ai"] = [{k: int(getattr(x, k)) for k, _ in x._fields_} for x in self.ai]
+        return d
 
 
 class Tuning(C.Structure):
@@ -278,8 +340,11 @@ EXPORTS = [
     "ppe_portscan_create", "ppe_portscan_destroy", "ppe_portscan_attach", "ppe_portscan_clock", "ppe_portscan_set",
     "ppe_portscan_age", "ppe_portscan_info", "ppe_portscan_dump", "ppe_portscan_last_error",
     "ppe_format_pkt_stat_ps", "ppe_format_fw_config",
+    "ppe_attack_create", "ppe_attack_destroy", "ppe_attack_attach", "ppe_attack_set", "ppe_attack_clock",
+    "ppe_attack_tick", "ppe_attack_ports", "ppe_attack_info", "ppe_attack_clear_stat", "ppe_attack_last_error",
+    "ppe_format_attack_stat", "ppe_format_pkt_stat_atk",
     # csrc/ppe_internal.h: the host-only launch planner (internal helpers, not part of the public headers)
-    "ppe_plan_image", "ppe_pick_groups", "ppe_pick_portscan",
+    "ppe_plan_image", "ppe_pick_groups", "ppe_pick_portscan", "ppe_pick_attack",
     # ppe_acl.h
     "ppe_rule_list_init", "ppe_rule_list_free", "Rule_add", "Rule_del_by_id", "Rule_del_all",
     "Rule_duplicate_check", "Rule_Load_Line", "ppe_rule_load_file", "DP_Acl_Rule_Init", "DP_Acl_Load_Rule",
@@ -398,6 +463,20 @@ def _open(p: Path, mode, strict: bool = True) -> C.CDLL:
         "ppe_plan_image": ([vp, u32, C.POINTER(Tuning), C.c_int, C.POINTER(Plan)], C.c_int),
         "ppe_pick_groups": ([u32, u32], u32),
         "ppe_pick_portscan": ([C.c_int, C.c_int, u32], u32),
+        "ppe_pick_attack": ([C.c_int, C.c_int], u32),
+        "ppe_attack_create": ([vp, C.POINTER(AttackCfg), C.POINTER(vp)], C.c_int),
+        "ppe_attack_destroy": ([vp], C.c_int),
+        "ppe_attack_attach": ([vp, vp], C.c_int),
+        "ppe_attack_set": ([vp, C.POINTER(AttackCfg)], C.c_int),
+        "ppe_attack_clock": ([vp, u64], C.c_int),
+        "ppe_attack_tick": ([vp, u64], C.c_int),
+        "ppe_attack_ports": ([vp, C.POINTER(vp), u32], C.c_int),
+        "ppe_attack_info": ([vp, C.POINTER(AttackInfo)], C.c_int),
+        "ppe_attack_clear_stat": ([vp], C.c_int),
+        "ppe_attack_last_error": ([vp], C.c_char_p),
+        "ppe_format_attack_stat": ([C.POINTER(AttackInfo), C.c_char_p, C.c_size_t], C.c_int),
+        "ppe_format_pkt_stat_atk": ([C.POINTER(Counters), C.POINTER(DefragInfo), C.c_int, C.POINTER(PortScanInfo),
+                                     C.POINTER(AttackInfo), C.c_char_p, C.c_size_t], C.c_int),
         "ppe_rule_list_init": ([], C.c_int),
         "ppe_rule_list_free": ([], None),
         "Rule_add": ([vp, C.POINTER(u32)], C.c_int),

@@ -117,6 +117,10 @@ class DeviceSteerOps:
         """A port-scan table is attached to this engine (Engine.portscan; ppe_classify_flow then returns PPE_ENOTSUP)."""
         return getattr(self.eng, "portscan_attached", None) is not None
 
+    def attack_attached(self) -> bool:
+        """Attack monitors are attached to this engine (Engine.attack; ppe_classify_flow then returns PPE_ENOTSUP)."""
+        return getattr(self.eng, "attack_attached", None) is not None
+
     def classify_flow(self, hdr, lens, cfg):
         t = self.torch
         n = lens.numel()
@@ -153,6 +157,9 @@ def steered_classify_flow(ops, dist, hdr, lens, cfg, world: int, rank: int) -> d
     if getattr(ops, "portscan_attached", None) and ops.portscan_attached():  # the same for an attached port-scan table
         raise PPEError(f"ppe_classify_flow failed: {abi.PPE_ENOTSUP}: a port-scan table is attached "
                        "(ppe_portscan_attach); the flow-table path does not support it")
+    if getattr(ops, "attack_attached", None) and ops.attack_attached():  # and for attached attack monitors
+        raise PPEError(f"ppe_classify_flow failed: {abi.PPE_ENOTSUP}: attack monitors are attached "
+                       "(ppe_attack_attach); the flow-table path does not support them")
     perm, counts, send_hdr, send_len = steer_prepare(ops, hdr, lens, cfg, world, rank)
     send_counts = counts.to(torch.int64)
     recv_counts = torch.empty_like(send_counts)

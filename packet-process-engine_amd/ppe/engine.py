@@ -231,6 +231,15 @@ class Engine:
             ps.attach()
         return ps
 
+    # ---- attack monitors (ppe_attack_*, dataplane/src/attack/dp_attack.c) ----
+    def attack(self, cfg: "abi.AttackCfg | None" = None, attach: bool = True) -> "Attack":
+        """ppe_attack_create (cfg None: all-zero rules, hold 600 s) and, unless attach is false, ppe_attack_attach: later
+        ppe_classify / ppe_classify_batches launches run the land, SYN-flood and UDP-flood monitors."""
+        a = Attack(self, cfg)
+        if attach:
+            a.attach()
+        return a
+
     def timing(self, on: bool = True):
         self._check(self.lib.ppe_timing_enable(self.ctx, 1 if on else 0), "ppe_timing_enable")
 
@@ -404,3 +413,68 @@ class PortScan:
         if n.value:
             self._check(self.lib.ppe_portscan_dump(self.h, ent.ctypes.data, n.value, C.byref(n)), "ppe_portscan_dump")
         return ent
+
+
+class Attack:
+    """The attack monitors of one Engine (ppe_attack_create): land, SYN flood, SYN count and UDP flood on the stateless
+    classify path (dataplane/src/attack/dp_attack.c).  Every call goes through libppe_hip.so."""
+
+    def __init__(self, engine: Engine, cfg: "abi.AttackCfg | None" = None):
+        self.eng = engine
+        self.lib = engine.lib
+        self.h = C.c_void_p()
+        self._ports = None  # keeps the caller's port arrays alive while they are in force
+        rc = self.lib.ppe_attack_create(engine.ctx, C.byref(cfg) if cfg is not None else None, C.byref(self.h))
+        if rc != 0:
+            raise PPEError(f"ppe_attack_create failed: {rc}")
+
+    def _check(self, rc, what):
+        if rc != 0:
+            err = self.lib.ppe_attack_last_error(self.h)
+            raise PPEError(f"{what} failed: {rc}: {err.decode() if err else ''}")
+
+    def attach(self):
+        self.eng._check(self.lib.ppe_attack_attach(self.eng.ctx, self.h), "ppe_attack_attach")
+        self.eng.attack_attached = self
+
+    def detach(self):
+        self.eng._check(self.lib.ppe_attack_attach(self.eng.ctx, None), "ppe_attack_attach")
+        self.eng.attack_attached = None
+
+    def close(self):
+        if self.h:
+            self.lib.ppe_attack_destroy(self.h)  # (detaches it first)
+            if getattr(self.eng, "attack_attached", None) is self:
+                self.eng.attack_attached = None
+            self.h = C.c_void_p()
+
+    def set(self, cfg: "abi.AttackCfg"):
+        """The rule file load (and flood_hold_time): ordered with the launches enqueued before and after."""
+        self._check(self.lib.ppe_attack_set(self.h, C.byref(cfg)), "ppe_attack_set")
+
+    def clock(self, now_seconds: int):
+        self._check(self.lib.ppe_attack_clock(self.h, int(now_seconds)), "ppe_attack_clock")
+
+    def tick(self, now_seconds: int):
+        """DP_Attack_Info_Update, once a second in the reference."""
+        self._check(self.lib.ppe_attack_tick(self.h, int(now_seconds)), "ppe_attack_tick")
+
+    def ports(self, arrays):
+        """arrays: per batch a torch uint8 cuda tensor (one input-port byte per packet) or None; None clears."""
+        arrays = list(arrays) if arrays is not None else []
+        tab = (C.c_void_p * max(1, len(arrays)))(*[(t.data_ptr() if t is not None else None) for t in arrays])
+        self._check(self.lib.ppe_attack_ports(self.h, tab if arrays else None, len(arrays)), "ppe_attack_ports")
+        self._ports = arrays
+
+    def info(self) -> dict:
+        i = abi.AttackInfo()
+        self._check(self.lib.ppe_attack_info(self.h, C.byref(i)), "ppe_attack_info")
+        return i.as_dict()
+
+    def info_struct(self) -> "abi.AttackInfo":
+        i = abi.AttackInfo()
+        self._check(self.lib.ppe_attack_info(self.h, C.byref(i)), "ppe_attack_info")
+        return i
+
+    def clear_stat(self):
+        self._check(self.lib.ppe_attack_clear_stat(self.h), "ppe_attack_clear_stat")
