@@ -618,7 +618,8 @@ const char *ppe_portscan_last_error(ppe_portscan_t *ps);
  * ppe_attack_set, _tick and _clear_stat are tiny kernels enqueued on the stream of the context's latest classify call
  * (the legacy default stream before the first): ordered with the launches enqueued before and after, no
  * synchronisation.  The caller orders its classify calls (one stream), as with the port-scan table.
- * With an object attached ppe_classify_flow and ppe_classify_host return PPE_ENOTSUP before touching anything.
+ * With an object attached ppe_classify_flow and ppe_classify_host return PPE_ENOTSUP before touching anything (the
+ * flow-table path has an attachment point of its own, ppe_flow_attack_attach below).
  * A new context has nothing attached: every output and counter is as without this interface. */
 #define PPE_ATTACK_PORTS 4
 typedef struct {                 /* packet_detect (dp_attack.h:26-33) */
@@ -653,6 +654,31 @@ int  ppe_attack_create(ppe_ctx_t *ctx, const ppe_attack_cfg_t *cfg, ppe_attack_t
  * ppe_ctx_destroy neither detaches nor destroys it (the same holds for ppe_portscan_destroy) */
 int  ppe_attack_destroy(ppe_attack_t *atk);
 int  ppe_attack_attach(ppe_ctx_t *ctx, ppe_attack_t *atk);        /* NULL detaches */
+/* ---- The same monitors on the flow-table path (ppe_classify_flow), the reference's own order: Decode -> DecodeIPV4 /
+ * DecodeTCP (monitors) -> FlowHandlePacket -> FlowFind | syn_check -> ACL -> FlowAdd ----
+ * While an object is attached here, ppe_classify_flow runs the monitors above with two differences:
+ *   - a packet a monitor drops never reaches FlowHandlePacket: no FlowFind, no slot claimed, no flow record, no
+ *     FlowUpdate and no last-seen store (also for a packet of a live flow), no PPE_F_FLOW / TOCLIENT / NEWFLOW; it is
+ *     not a miss.  Its outputs and counters are the stateless path's (status 25-28, drop, acl_hit -1, flow hash 0,
+ *     PPE_F_L4 clear, PPE_F_TCP | PPE_F_SYN on 25-27, ports 0; the RX chain up to IPV4_RX_OK, then OUT_DROP).  The
+ *     monitors see a packet whether or not its flow exists (a SYN of a live flow counts in syn_accum);
+ *   - syncount_accum counts flow creations, as DP_Attack_SynCountMonitor in FlowAdd behind flow_item_alloc does
+ *     (flow.c:120-158): +1 on the packet's port only for a TCP SYN packet that ends up with PPE_F_NEWFLOW.  Not a
+ *     later SYN of the same 5-tuple in the batch, not a SYN of a live flow, not a creator refused with
+ *     PPE_ST_FLOW_NOMEM, not an ACL drop or FLOW_TCP_NO_SYN_FIRST, not a UDP or non-SYN TCP packet that creates a flow.
+ *     (The stateless path counts every forwarded SYN: there every packet is a flow miss.)
+ * Everything else is as above: the tick, set, clock, info, clear_stat, the show texts, the hold arming.  Still not
+ * built: syncount_accum's decrements (the session machine), per-fragment counting, ICMP.
+ * ppe_classify_flow is one batch per call: it reads entry 0 of ppe_attack_ports' table (NULL or none: port 0), at the
+ * call, by value.  Calls go through one stream or are ordered by the caller; ppe_attack_set / _tick apply to the
+ * launches enqueued after them, without a synchronise.
+ * The context's stateless calls (ppe_classify, ppe_classify_batches, ppe_classify_host) do not see an object attached
+ * here: they run the kernels without monitors.  An object is attached to at most one of the two points: attaching
+ * one that the other point holds returns PPE_EINVAL ("detach first"), as does an object of another context.
+ * ppe_attack_destroy detaches from whichever point holds the object; ppe_flow_destroy leaves the attachment (it is
+ * the context's, like the table pointer).  ppe_classify_flow still returns PPE_ENOTSUP, before touching anything,
+ * with stream tracking on, a port-scan table attached, or an object attached with ppe_attack_attach. */
+int  ppe_flow_attack_attach(ppe_ctx_t *ctx, ppe_attack_t *atk);   /* NULL detaches */
 /* the rule file load / DP_Attack_Del_All / dp_attack_defend_time_set: the rules and hold_seconds (the state stays) */
 int  ppe_attack_set(ppe_attack_t *atk, const ppe_attack_cfg_t *cfg);
 int  ppe_attack_clock(ppe_attack_t *atk, uint64_t now_seconds);   /* by value with the launches enqueued afterwards */

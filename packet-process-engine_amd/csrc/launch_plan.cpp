@@ -318,4 +318,10 @@ uint32_t ppe_pick_attack(int flow, int attached) {
     return (!flow && attached) ? 1u : 0u;  // the monitors sit in the decoders (decode-ipv4.c:141-149, decode-tcp.c:162-173)
 }
 
+// the same monitors ahead of FlowFind, with syncount_accum counted per created flow (FlowAdd, flow.c:151-154): only a
+// flow-table launch of a context with an object attached for that path (ppe_flow_attack_attach)
+uint32_t ppe_pick_attack_flow(int flow, int flow_attached) {
+    return (flow && flow_attached) ? 1u : 0u;
+}
+
 }  // extern "C"

@@ -200,6 +200,7 @@ struct ppe_ctx {
     uint32_t max_groups = 8;
     ppe_portscan_table *ps = nullptr;  // ppe_portscan_attach
     ppe_attack *atk = nullptr;         // ppe_attack_attach
+    ppe_attack *atk_flow = nullptr;    // ppe_flow_attack_attach: ppe_classify_flow's monitors (never the same object as atk)
     FlowTable *flow = nullptr;  // ppe_flow_create
     LookupStage lk;             // ppe_acl_lookup_host
     uint32_t *d_steer = nullptr;  // ppe_steer_partition: per-tile owner counts / offsets
@@ -662,6 +663,15 @@ int launch(ppe_ctx *c, const ppe_batch_t *in, const ppe_result_t *out, uint32_t 
         a.atk_pbase = atk_pbase;
         a.atk_now = t->now;
         a.atk_hold = t->cfg.hold_seconds;
+        t->stream = s;
+    }
+    if (ppe_pick_attack_flow(fl != nullptr, c->atk_flow != nullptr)) {  // the same for the flow-table launch (one batch)
+        ppe_attack *t = c->atk_flow;
+        a.fatk_st = t->d_st;
+        a.fatk_slots = t->d_slots;
+        a.fatk_pb = t->h_ports.empty() ? nullptr : t->h_ports[0];
+        a.fatk_now = t->now;
+        a.fatk_hold = t->cfg.hold_seconds;
         t->stream = s;
     }
     int rslot = 0;
@@ -1529,6 +1539,7 @@ int ppe_attack_destroy(ppe_attack_t *t) {
     (void)hipSetDevice(t->ctx->device);
     (void)hipDeviceSynchronize();
     if (t->ctx->atk == t) t->ctx->atk = nullptr;
+    if (t->ctx->atk_flow == t) t->ctx->atk_flow = nullptr;
     atk_free_retired(t, true);
     if (t->d_ports) (void)hipFree((void *)t->d_ports);
     (void)hipFree(t->d_st);
@@ -1540,7 +1551,20 @@ int ppe_attack_destroy(ppe_attack_t *t) {
 int ppe_attack_attach(ppe_ctx_t *c, ppe_attack_t *t) {
     if (!c) return PPE_EINVAL;
     if (t && t->ctx != c) return fail(c, PPE_EINVAL, "ppe_attack_attach: the object belongs to another context");
+    if (t && c->atk_flow == t)
+        return fail(c, PPE_EINVAL, "ppe_attack_attach: the object is attached with ppe_flow_attack_attach: detach first");
     c->atk = t;
+    return PPE_OK;
+}
+
+// The flow-table path's attachment point: the same object and monitors, but syncount_accum counts the flows TCP SYN
+// packets create (FlowAdd, flow.c:151-154) instead of every forwarded SYN, so an object runs under one of the two
+int ppe_flow_attack_attach(ppe_ctx_t *c, ppe_attack_t *t) {
+    if (!c) return PPE_EINVAL;
+    if (t && t->ctx != c) return fail(c, PPE_EINVAL, "ppe_flow_attack_attach: the object belongs to another context");
+    if (t && c->atk == t)
+        return fail(c, PPE_EINVAL, "ppe_flow_attack_attach: the object is attached with ppe_attack_attach: detach first");
+    c->atk_flow = t;
     return PPE_OK;
 }
 
@@ -1973,7 +1997,8 @@ int ppe_classify_flow(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *o
     // PortScan_Detect runs on flow misses only (flow.c:196-215), and whether a packet misses depends on the verdicts
     // of the packets before it: not built
     if (c->ps) return fail(c, PPE_ENOTSUP, "ppe_classify_flow with a port-scan table attached is not supported");
-    // the monitors are built for the stateless kernels only (syncount_accum counts flow creations, FlowAdd)
+    // an object attached for the stateless path counts every forwarded SYN in syncount_accum; here it counts flow
+    // creations (FlowAdd): that takes ppe_flow_attack_attach
     if (c->atk) return fail(c, PPE_ENOTSUP, "ppe_classify_flow with attack monitors attached is not supported");
     int rc = check_batch(c, in, cfg);
     if (rc != PPE_OK || in->n == 0) return rc;
@@ -2023,11 +2048,16 @@ int ppe_classify_flow(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *o
     k.now = cfg ? cfg->now_seconds : 0u;
     k.nslots = t.nslots;
     k.cslots = c->d_cslots;
+    if (ppe_pick_attack_flow(1, c->atk_flow != nullptr)) {  // syncount_accum: the flows this batch's SYNs create
+        k.atk_slots = c->atk_flow->d_slots;
+        k.atk_pb = c->atk_flow->h_ports.empty() ? nullptr : c->atk_flow->h_ports[0];
+    }
     // 2. the post-classify launch: finalize (grid-stride over the miss-tile list, usually short: at most one
     // workgroup per CU) and, beside it, the found flows' counters and last-seen times, one workgroup per owner
     // (disjoint from the slots finalize touches).  When the host's bound says the pool may overflow, finalize checks
     // the exact counts and, on an overflow, marks the creators and has its workgroup 0 revoke those past the pool's
     // room first.
+    // (fg <= n_cu <= max_grid: the finalize workgroups' indices stay inside the monitors' max_grid count slots)
     const uint32_t fg = std::min(std::min(flow_grid(c, (in->n + 63u) / 64u, PPE_FLOW_POST_BLOCK / 64u), c->n_cu),
                                  t.fin_cap ? t.fin_cap : c->n_cu);
     const bool may_overflow = t.live_ub + in->n > t.capacity;

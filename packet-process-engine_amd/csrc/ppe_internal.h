@@ -119,7 +119,16 @@ struct ppe_flow_kargs {
     uint32_t revoke;              /* finalize: the host's bound says the pool may overflow (check, rank, revoke) */
     uint32_t fin_wgs;             /* post-classify launch: workgroups [0, fin_wgs) finalize, the next upd_owners update */
     unsigned long long *cslots;   /* counter slots (one per workgroup) */
-    struct ppe_flowdev dst;       /* rehash target */
+    union {
+        struct ppe_flowdev dst;   /* rehash target */
+        /* the post launch with attack monitors flow-attached (it has no rehash target: the same bytes, so the block
+           keeps its size; atk_slots NULL: without): syncount_accum of the flows TCP SYN packets create
+           (DP_Attack_SynCountMonitor in FlowAdd, flow.c:151-154) */
+        struct {
+            unsigned long long *atk_slots; /* [>= fin_wgs][PPE_ATK_SLOT_WORDS]: finalize workgroup b adds into slot b */
+            const uint8_t *atk_pb;         /* the batch's port bytes or NULL (port 0) */
+        };
+    };
 };
 
 /* batches per launch whose descriptors travel in the kernel arguments (32 × 96 B); a launch over more batches reads
@@ -130,10 +139,26 @@ struct ppe_flow_kargs {
 
 /* Kernel launch parameters, passed by value. */
 struct ppe_kargs {
+    union {
     struct ppe_bdesc batch[PPE_MAX_BATCH];  /* [0, nbatch) when nbatch <= PPE_MAX_BATCH.  The grid's waves split into
                                                G = min(waves, nbatch, max_groups) batch groups that run concurrently:
                                                group g takes batches g, g + G, ... in turn (no barrier between them),
                                                its waves striding over each batch's tiles */
+    /* Flow-table launches of a context with attack monitors flow-attached (ppe_flow_attack_attach; the FLOW + ATK
+       kernels, csrc/ppe_kernels_attack_flow.hip).  There `flow` and the monitors' arguments below do meet; a
+       flow-table launch is one batch, so its monitor arguments lie in the bytes of batch[1]: the argument block keeps
+       its size and every offset (the implicit arguments behind it included), and no other kernel reads them
+       (fatk_st NULL: the flow kernels without the monitors).  The batch's port bytes travel by value */
+    struct {
+        struct ppe_bdesc fatk_batch0;        /* = batch[0] */
+        unsigned long long *fatk_st;         /* as atk_st */
+        unsigned long long *fatk_slots;      /* as atk_slots; word 3 port + 2 (syncount_accum) is the post launch's */
+        const uint8_t *fatk_pb;              /* the batch's port bytes (entry 0 of ppe_attack_ports' table) or NULL */
+        uint64_t fatk_now;                   /* as atk_now */
+        uint32_t fatk_hold;                  /* as atk_hold */
+        uint32_t fatk_pad;
+    };
+    };
     const struct ppe_bdesc *ring;           /* non-NULL: the nbatch descriptors are ring[0, nbatch) in device memory
                                                (one persistent launch over a whole queue of batches, nbatch beyond
                                                PPE_MAX_BATCH); batch[0] then repeats ring[0] */
@@ -391,6 +416,10 @@ uint32_t ppe_pick_portscan(int flow, int attached, uint32_t able);
 /* 1: the launch takes the kernels with the attack monitors (ATK): a stateless launch of a context with an object
  * attached (ppe_attack_attach), and no other launch */
 uint32_t ppe_pick_attack(int flow, int attached);
+/* 1: the launch takes the flow-table kernels with the attack monitors (FLOW + ATK) and the post kernel that counts
+ * syncount_accum per created flow: a flow-table launch of a context with an object flow-attached
+ * (ppe_flow_attack_attach), and no other launch */
+uint32_t ppe_pick_attack_flow(int flow, int flow_attached);
 /* the monitors' set / tick / clear kernel (csrc/ppe_attack.hip), stream-ordered.  Returns hipError_t */
 int ppe_launch_attack_ctl(const struct ppe_atk_kargs *a, void *stream);
 /* one kernel of the port-scan pre-pass (csrc/ppe_portscan.hip), grid sized from the arguments.  Returns hipError_t */

@@ -8,7 +8,9 @@
  *      the reference's check order and uint16/uint8 arithmetic — citations inline);
  *   2b. with attack monitors attached (ppe_attack_attach; the ATK instantiations, csrc/ppe_kernels_attack*.hip): the
  *      land / SYN-flood / UDP-flood verdicts inside decode(), from one decision word per launch, and the per-port
- *      accumulators in spare counter bins, flushed once per workgroup;
+ *      accumulators in spare counter bins, flushed once per workgroup; flow-attached (ppe_flow_attack_attach; the
+ *      FLOW + ATK instantiations, csrc/ppe_kernels_attack_flow.hip) the same ahead of the flow lookup, a monitor drop
+ *      leaving decode() like a decode error, and syncount_accum counted by the post launch per SYN-created flow;
  *   3. flow_hashfn (TluHash ×3, dataplane/src/flow/tluhash.h:7-35);
  *   4. on the flow-miss path: syn_check, then the ACL decision-tree walk (image v3, ppe_image.h: one LDS round trip
  *      and four VALU per level, the classifier staged in LDS when it fits) and the leaf's rule check;
@@ -1382,6 +1384,20 @@ struct AtkWave {
 struct AtkNone {};
 template <bool ATK> struct AtkSel { typedef AtkWave type; };
 template <> struct AtkSel<false> { typedef AtkNone type; };
+// the monitors' launch arguments: a flow-table launch (FLOW + ATK) carries its own behind the bytes `flow` shares with
+// the stateless ones (ppe_kargs.fatk_*)
+template <bool FLOW> __device__ __forceinline__ unsigned long long *atk_state(const ppe_kargs &a) {
+    if constexpr (FLOW) return a.fatk_st;
+    else return a.atk_st;
+}
+template <bool FLOW> __device__ __forceinline__ unsigned long long *atk_slot_base(const ppe_kargs &a) {
+    if constexpr (FLOW) return a.fatk_slots;
+    else return a.atk_slots;
+}
+template <bool FLOW> __device__ __forceinline__ uint64_t atk_hold_until(const ppe_kargs &a) {
+    if constexpr (FLOW) return a.fatk_now + a.fatk_hold;
+    else return a.atk_now + a.atk_hold;
+}
 // the packet's udp_accum / syn_accum count, from the class and port bits decode() left in its flags
 __device__ __forceinline__ void atk_count(uint32_t *bins, uint32_t flags) {
     const uint32_t cls = (flags >> PPE_ATK_CLS_SHIFT) & 3u;
@@ -1393,8 +1409,12 @@ __device__ __forceinline__ void atk_count(uint32_t *bins, uint32_t flags) {
 // cost C1's kernel 2 spilled VGPRs with tracking off), so with tracking off the kernels contain none of it.
 // PSC: the port-scan detector's drop mask (a table with able = 1 attached, ppe_portscan_attach; stateless kernels only;
 // csrc/ppe_kernels_portscan.hip), a template parameter for the same reason; combines with STM.
-// ATK: the attack monitors (an object attached, ppe_attack_attach; stateless kernels only;
+// ATK: the attack monitors (an object attached, ppe_attack_attach: the stateless kernels,
 // csrc/ppe_kernels_attack*.hip), a template parameter for the same reason; combines with STM and PSC.
+// FLOW + ATK (an object attached with ppe_flow_attack_attach, csrc/ppe_kernels_attack_flow.hip): the monitors sit in
+// the decoders, ahead of FlowFind, so a packet they drop leaves decode() as a decode error does (no PPE_F_L4): no
+// lookup, no claim, no record, not a miss.  syncount_accum is not counted here: it counts the flows SYNs create,
+// which the post launch knows (flow_finalize_wg).
 template <int MODE, int PF, int BLOCK, bool FLOW, bool PART = false, bool STM = false, bool PSC = false,
           bool ATK = false>
 __global__ __launch_bounds__(BLOCK, (PF == PF_MULTI && !FLOW) ? PPE_MT_WAVES
@@ -1413,7 +1433,7 @@ void ppe_classify_kernel(ppe_kargs a) {
     constexpr bool KEYS = MT == 1 && !CUT;  // node walks: per-wave key slots in LDS
     static_assert(!(STM && FLOW), "stream tracking: stateless kernels only");
     static_assert(!(PSC && FLOW), "port-scan mask: stateless kernels only");
-    static_assert(!(ATK && FLOW), "attack monitors: stateless kernels only");
+    static_assert(!(ATK && FLOW && (STM || PSC || PART)), "flow-table kernels: the attack monitors alone");
     const uint32_t stm = STM ? a.stream : 0u;
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     using L = Lds<BLOCK, KEYS, FLOW ? 4u * PPE_UPD_OWNERS * (1u + (PPE_UPD_LDS ? PPE_UPD_CAP : 0u)) : 0u>;
@@ -1441,6 +1461,10 @@ void ppe_classify_kernel(ppe_kargs a) {
     // (the ring is read through the constant address space: uniform addresses there become scalar loads, so the
     // descriptor lives in SGPRs as the kernel-argument one does)
     static_assert(sizeof(ppe_bdesc) == 96, "descriptor = 6 x 16 B");
+    static_assert(offsetof(ppe_kargs, fatk_st) == sizeof(ppe_bdesc) &&
+                      offsetof(ppe_kargs, fatk_pad) + 4u <= 2u * sizeof(ppe_bdesc) && offsetof(ppe_kargs, ring) ==
+                      PPE_MAX_BATCH * sizeof(ppe_bdesc),
+                  "a flow launch's monitor arguments lie in batch[1]");
     auto bdesc = [&](uint32_t bi) -> ppe_bdesc {
         if (!a.ring) return a.batch[bi];
         typedef const __attribute__((address_space(4))) u32x4 *cq_t;
@@ -1454,7 +1478,10 @@ void ppe_classify_kernel(ppe_kargs a) {
     // ATK: the decision word (one uniform load per launch: nothing changes it between two ticks) and the current
     // batch's port bytes, looked up wherever B changes.  Without ATK the object is empty and nothing below names it
     typename AtkSel<ATK>::type atk;
-    if constexpr (ATK) {
+    if constexpr (ATK && FLOW) {  // (one batch per launch: its port bytes travel by value)
+        atk.word = (uint32_t)a.fatk_st[PPE_ATK_WORD];
+        atk.pb = a.fatk_pb;
+    } else if constexpr (ATK) {
         atk.word = (uint32_t)a.atk_st[PPE_ATK_WORD];
         atk.batch(a, wave_live ? grp : 0u);
     }
@@ -1521,9 +1548,10 @@ void ppe_classify_kernel(ppe_kargs a) {
     auto finish = [&](uint32_t tile, uint32_t p, bool valid, const Dec &k, uint32_t fh, int32_t hit, bool pend,
                       uint32_t sfw) {
         uint32_t st = k.st;
-        if constexpr (ATK) {
+        if constexpr (ATK && !FLOW) {
             // DP_Attack_SynCountMonitor in FlowAdd (flow.c:151-154): a TCP SYN the ACL forwarded, after the port-scan
-            // mask and before StreamTcp's verdict (flow.c:243 precedes :311)
+            // mask and before StreamTcp's verdict (flow.c:243 precedes :311).  (FLOW: FlowAdd runs only for the packet
+            // that creates its flow, known to the post launch, which counts it)
             if (!(PPE_ABLATE & 2) && valid && st == PPE_ST_ACL_FW &&
                 (k.flags & (PPE_F_TCP | PPE_F_SYN)) == (PPE_F_TCP | PPE_F_SYN))
                 atomicAdd(&bins[PPE_ATK_BIN_SYNCNT + (((sfw >> PPE_ATK_PORT_SHIFT) & 3u) << 5)], 1u);
@@ -1874,7 +1902,7 @@ void ppe_classify_kernel(ppe_kargs a) {
     } else
     for (uint32_t bi = grp; wave_live && bi < a.nbatch; bi += ngroups) {
         if (bi != grp) B = bdesc(bi);
-        if constexpr (ATK)
+        if constexpr (ATK && !FLOW)
             if (bi != grp) atk.batch(a, bi);
         const uint32_t ntiles = (B.n + 63u) >> 6;
         for (uint32_t tile = wtile; tile < ntiles; tile += stride_waves) {
@@ -1896,8 +1924,8 @@ void ppe_classify_kernel(ppe_kargs a) {
         if (c) {
             if constexpr (ATK) {
                 const uint32_t st = b & 31u, port = (b >> 5) & 3u;
-                unsigned long long *ps = a.atk_st + PPE_ATK_PORT0 + PPE_ATK_PORT_STRIDE * port;
-                unsigned long long *slot = a.atk_slots + (size_t)blockIdx.x * PPE_ATK_SLOT_WORDS;
+                unsigned long long *ps = atk_state<FLOW>(a) + PPE_ATK_PORT0 + PPE_ATK_PORT_STRIDE * port;
+                unsigned long long *slot = atk_slot_base<FLOW>(a) + (size_t)blockIdx.x * PPE_ATK_SLOT_WORDS;
                 if (st >= PPE_ATK_BIN_UDP) {
                     // this workgroup's share of a port's udp_accum / syn_accum / syncount_accum: one add per non-empty
                     // bin into the workgroup's own slot (one word shared by every workgroup cost 7 us per 1M
@@ -1909,11 +1937,11 @@ void ppe_classify_kernel(ppe_kargs a) {
                     __hip_atomic_fetch_add(&slot[3u * port + (st - PPE_ATK_BIN_UDP)], (unsigned long long)c,
                                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     const uint32_t arm = udp ? PPE_ATK_UDP_ARM : st == PPE_ATK_BIN_SYN ? PPE_ATK_SYN_ARM : 0u;
-                    if (((uint32_t)a.atk_st[PPE_ATK_WORD] >> (6u * port)) & arm) {
+                    if (((uint32_t)atk_state<FLOW>(a)[PPE_ATK_WORD] >> (6u * port)) & arm) {
                         unsigned long long *hold = &ps[udp ? PPE_ATK_UDP_HOLD : PPE_ATK_SYN_HOLD];
                         if (__hip_atomic_load(hold, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0ull &&
                             atomicCAS(hold, 0ull, 1ull) == 0ull)
-                            __hip_atomic_store(hold + 1, (unsigned long long)(a.atk_now + a.atk_hold), __ATOMIC_RELAXED,
+                            __hip_atomic_store(hold + 1, (unsigned long long)atk_hold_until<FLOW>(a), __ATOMIC_RELAXED,
                                                __HIP_MEMORY_SCOPE_AGENT);
                     }
                     continue;
@@ -2040,16 +2068,23 @@ __device__ __forceinline__ void flow_revoke(const ppe_flow_kargs &a, uint32_t *p
 }
 
 // finalize, on the first nwg workgroups of the post-classify launch (ppe_flow_post_kernel)
-template <int BLOCK>
+// ATK (attack monitors flow-attached, ppe_flow_attack_attach; csrc/ppe_kernels_attack_flow.hip): a TCP SYN packet
+// that creates its flow adds 1 to its input port's syncount_accum (DP_Attack_SynCountMonitor sits in FlowAdd behind
+// flow_item_alloc, flow.c:151-154: not a packet that finds the flow, not a revoked creator).  Counted per port and
+// tile by ballot, summed per workgroup in LDS, one add per non-empty port into the workgroup's own count slot
+template <int BLOCK, bool ATK = false>
 __device__ __forceinline__ void flow_finalize_wg(const ppe_flow_kargs &a, uint32_t nwg) {
     __shared__ uint32_t bins[PPE_NBINS];
     __shared__ uint32_t lcnt[32];
     __shared__ uint32_t part[BLOCK];
     __shared__ uint32_t rev_s;
     __shared__ unsigned long long room_s;
+    __shared__ uint32_t syn_new[ATK ? 4 : 1];  // ATK: this workgroup's SYN-created flows per port
     const uint32_t tid = threadIdx.x;
     for (uint32_t i = tid; i < PPE_NBINS; i += BLOCK) bins[i] = 0;
     if (tid < 32u) lcnt[tid] = 0;
+    if constexpr (ATK)
+        if (tid < 4u) syn_new[tid] = 0;
     // revoke: when the host's bound says the pool may overflow, every workgroup checks the exact counts; on an
     // overflow every workgroup marks the creators of its miss tiles (tile_new) and arrives on a counter, workgroup 0
     // (dispatched first) waits for all arrivals (the grid, at most two workgroups per CU, is resident), ranks and
@@ -2151,6 +2186,7 @@ __device__ __forceinline__ void flow_finalize_wg(const ppe_flow_kargs &a, uint32
         const uint32_t v = valid ? a.verdict[p] : 0u;
         uint32_t act = (v >> 8) & 0xffu;
         bool is_new = false, is_rev = false;
+        bool syn_created = false;  // ATK: is_new by a TCP SYN
         if ((mask >> w.lane) & 1ull) {
             const uint4 r = rec[p];
             const uint32_t prov = (r.w >> 8) & 0xffu;
@@ -2172,6 +2208,7 @@ __device__ __forceinline__ void flow_finalize_wg(const ppe_flow_kargs &a, uint32
                         st = PPE_ST_ACL_FW;
                         is_new = true;
                         flags |= PPE_F_NEWFLOW | flow_account(a.f, s, r.x, r.z, r.x, r.z, a.len[p], a.now);
+                        if constexpr (ATK) syn_created = (flags & (PPE_F_TCP | PPE_F_SYN)) == (PPE_F_TCP | PPE_F_SYN);
                         ((uint4 *)a.f.keys)[(size_t)(PPE_FLOW_SLOT_WORDS / 4u) * s] =
                             make_uint4(r.x, r.y, r.z, PPE_FS_LIVE(r.w & 0xffu));
                     }
@@ -2193,6 +2230,17 @@ __device__ __forceinline__ void flow_finalize_wg(const ppe_flow_kargs &a, uint32
         compact_tile(a.fw_idx, a.drop_idx, a.tile_cnt, a.n, 0u, t, w.lane, valid, act, ~0u, a.part8);
         created += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(is_new));
         revoked += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(is_rev));
+        if constexpr (ATK) {
+            if (__builtin_amdgcn_ballot_w64(syn_created)) {  // (wave-uniform: most miss tiles of a warm table skip it)
+                uint32_t port = 0;
+                if (syn_created && a.atk_pb) port = (uint32_t)a.atk_pb[p] & 3u;  // (syn_created: p < n)
+#pragma unroll
+                for (uint32_t q = 0; q < 4u; ++q) {
+                    const uint32_t c = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(syn_created && port == q));
+                    if (w.lane == 0 && c) atomicAdd(&syn_new[q], c);
+                }
+            }
+        }
     }
     if (w.lane == 0 && created) {
         __hip_atomic_fetch_add(&a.f.ctl[PPE_FCTL_LIVE], (unsigned long long)created, __ATOMIC_RELAXED,
@@ -2214,6 +2262,10 @@ __device__ __forceinline__ void flow_finalize_wg(const ppe_flow_kargs &a, uint32
     if (tid < PPE_C__COUNT && lcnt[tid])
         __hip_atomic_fetch_add(&a.cslots[(size_t)blockIdx.x * PPE_CSLOT_WORDS + tid], (unsigned long long)lcnt[tid],
                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if constexpr (ATK)  // (behind the barriers above: every wave's LDS adds are in)
+        if (tid < 4u && syn_new[tid])
+            __hip_atomic_fetch_add(&a.atk_slots[(size_t)blockIdx.x * PPE_ATK_SLOT_WORDS + 3u * tid + 2u],
+                                   (unsigned long long)syn_new[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // FlowUpdate + FLOW_UPDATE_TIMESTAMP of the found packets (flow.c:163-178), owner-computed: workgroup o owns the
@@ -2358,6 +2410,14 @@ template <int BLOCK>
 __global__ __launch_bounds__(BLOCK) void ppe_flow_post_kernel(ppe_flow_kargs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t usm[];
     if (blockIdx.x < a.fin_wgs) flow_finalize_wg<BLOCK>(a, a.fin_wgs);
+    else flow_update_wg<BLOCK>(a, blockIdx.x - a.fin_wgs, usm);
+}
+// the same with attack monitors flow-attached: finalize also counts syncount_accum (a kernel of its own, instantiated
+// in csrc/ppe_kernels_attack_flow.hip: the one above contains none of it)
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void ppe_flow_post_attack_kernel(ppe_flow_kargs a) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t usm[];
+    if (blockIdx.x < a.fin_wgs) flow_finalize_wg<BLOCK, true>(a, a.fin_wgs);
     else flow_update_wg<BLOCK>(a, blockIdx.x - a.fin_wgs, usm);
 }
 
@@ -2638,6 +2698,31 @@ extern "C" int ppe_launch_classify_attack(
     const hipEvent_t e0 = (hipEvent_t)ev_start, e1 = (hipEvent_t)ev_stop;
     PPE_DISPATCH(launch_atk_t, a, grid, shmem, s, e0, e1);
 }
+#elif defined(PPE_TU_ATTACK_FLOW)
+// csrc/ppe_kernels_attack_flow.hip: this file again, exporting only the flow-table kernels with the attack monitors
+// (FLOW + ATK: the hoisted fetch over global / LDS / split images at 256 / 512 / 1024 threads) and the post kernel
+// whose finalize counts syncount_accum
+template <int M, int P, int B>
+static int launch_atk_flow_t(const ppe_kargs *a, uint32_t grid, size_t shmem, hipStream_t s, hipEvent_t e0,
+                             hipEvent_t e1) {
+    // (as without the monitors, the flow-table variant is built for the default tile fetch only)
+    hipExtLaunchKernelGGL((ppe_classify_kernel<M, PF_HOIST, B, true, false, false, false, true>), dim3(grid), dim3(B),
+                          shmem, s, e0, e1, 0, *a);
+    return (int)hipGetLastError();
+}
+extern "C" int ppe_launch_classify_attack_flow(const ppe_kargs *a, uint32_t grid, size_t shmem, int mode, int pipe,
+                                               int block, void *stream, void *ev_start, void *ev_stop) {
+    const hipStream_t s = (hipStream_t)stream;
+    const hipEvent_t e0 = (hipEvent_t)ev_start, e1 = (hipEvent_t)ev_stop;
+    if (mode == IMG_LDS) PPE_DISPATCH_B(launch_atk_flow_t, IMG_LDS, PF_HOIST, a, grid, shmem, s, e0, e1);
+    if (mode == IMG_SPLIT) PPE_DISPATCH_B(launch_atk_flow_t, IMG_SPLIT, PF_HOIST, a, grid, shmem, s, e0, e1);
+    PPE_DISPATCH_B(launch_atk_flow_t, IMG_GLOBAL, PF_HOIST, a, grid, shmem, s, e0, e1);
+}
+extern "C" int ppe_launch_flow_post_attack(const ppe_flow_kargs *a, uint32_t grid, size_t shmem, void *stream) {
+    hipLaunchKernelGGL(ppe_flow_post_attack_kernel<PPE_FLOW_POST_BLOCK>, dim3(grid), dim3(PPE_FLOW_POST_BLOCK), shmem,
+                       (hipStream_t)stream, *a);
+    return (int)hipGetLastError();
+}
 #elif defined(PPE_TU_STREAM)
 // csrc/ppe_kernels_stream.hip: this file again, exporting only the stateless kernels with StreamTcp's verdict (STM)
 template <int M, int P, int B>
@@ -2710,7 +2795,8 @@ extern "C" int ppe_launch_classify_portscan_stream(const ppe_kargs *a, uint32_t 
 typedef int ppe_launch_variant_fn(const ppe_kargs *a, uint32_t grid, size_t shmem, int mode, int pipe, int block,
                                   void *stream, void *ev_start, void *ev_stop);
 extern "C" ppe_launch_variant_fn ppe_launch_classify_attack, ppe_launch_classify_attack_stream,
-    ppe_launch_classify_attack_portscan, ppe_launch_classify_attack_portscan_stream;
+    ppe_launch_classify_attack_portscan, ppe_launch_classify_attack_portscan_stream, ppe_launch_classify_attack_flow;
+extern "C" int ppe_launch_flow_post_attack(const ppe_flow_kargs *a, uint32_t grid, size_t shmem, void *stream);
 
 template <int M, int P, int B>
 static int launch_t(const ppe_kargs *a, uint32_t grid, size_t shmem, hipStream_t s, hipEvent_t e0, hipEvent_t e1,
@@ -2763,6 +2849,8 @@ extern "C" int ppe_launch_classify(const ppe_kargs *a, uint32_t grid, int mode, 
     // a port-scan table attached and enabled: the kernels that read the pre-pass's drop mask, with or without StreamTcp
     // (same launch bounds and LDS again)
     // attack monitors attached: the kernels with them, alone or with either or both of the above (the same again)
+    if (flow && a->fatk_st)  // flow-attached (ppe_flow_attack_attach): the flow-table kernels with them
+        return ppe_launch_classify_attack_flow(a, grid, shmem, mode, pipe, block, stream, ev_start, ev_stop);
     if (!flow && a->atk_st) {
         ppe_launch_variant_fn *const f =
             a->psmask ? (a->stream ? ppe_launch_classify_attack_portscan_stream : ppe_launch_classify_attack_portscan)
@@ -2784,6 +2872,8 @@ extern "C" int ppe_launch_flow(int kind, const ppe_flow_kargs *a, uint32_t grid,
     const dim3 g(grid), b(PPE_FLOW_BLOCK);
     switch (kind) {
         case PPE_FLOW_K_POST:
+            if (a->atk_slots)  // attack monitors flow-attached: finalize counts syncount_accum
+                return ppe_launch_flow_post_attack(a, grid, a->f.upd_wgs ? PPE_UPD_HASH * 20u : 0u, stream);
             hipLaunchKernelGGL(ppe_flow_post_kernel<PPE_FLOW_POST_BLOCK>, g, dim3(PPE_FLOW_POST_BLOCK),
                                a->f.upd_wgs ? PPE_UPD_HASH * 20u : 0u, s, *a);
             break;

@@ -340,11 +340,11 @@ EXPORTS = [
     "ppe_portscan_create", "ppe_portscan_destroy", "ppe_portscan_attach", "ppe_portscan_clock", "ppe_portscan_set",
     "ppe_portscan_age", "ppe_portscan_info", "ppe_portscan_dump", "ppe_portscan_last_error",
     "ppe_format_pkt_stat_ps", "ppe_format_fw_config",
-    "ppe_attack_create", "ppe_attack_destroy", "ppe_attack_attach", "ppe_attack_set", "ppe_attack_clock",
+    "ppe_attack_create", "ppe_attack_destroy", "ppe_attack_attach", "ppe_flow_attack_attach", "ppe_attack_set", "ppe_attack_clock",
     "ppe_attack_tick", "ppe_attack_ports", "ppe_attack_info", "ppe_attack_clear_stat", "ppe_attack_last_error",
     "ppe_format_attack_stat", "ppe_format_pkt_stat_atk",
     # csrc/ppe_internal.h: the host-only launch planner (internal helpers, not part of the public headers)
-    "ppe_plan_image", "ppe_pick_groups", "ppe_pick_portscan", "ppe_pick_attack",
+    "ppe_plan_image", "ppe_pick_groups", "ppe_pick_portscan", "ppe_pick_attack", "ppe_pick_attack_flow",
     # ppe_acl.h
     "ppe_rule_list_init", "ppe_rule_list_free", "Rule_add", "Rule_del_by_id", "Rule_del_all",
     "Rule_duplicate_check", "Rule_Load_Line", "ppe_rule_load_file", "DP_Acl_Rule_Init", "DP_Acl_Load_Rule",
@@ -464,9 +464,11 @@ def _open(p: Path, mode, strict: bool = True) -> C.CDLL:
         "ppe_pick_groups": ([u32, u32], u32),
         "ppe_pick_portscan": ([C.c_int, C.c_int, u32], u32),
         "ppe_pick_attack": ([C.c_int, C.c_int], u32),
+        "ppe_pick_attack_flow": ([C.c_int, C.c_int], u32),
         "ppe_attack_create": ([vp, C.POINTER(AttackCfg), C.POINTER(vp)], C.c_int),
         "ppe_attack_destroy": ([vp], C.c_int),
         "ppe_attack_attach": ([vp, vp], C.c_int),
+        "ppe_flow_attack_attach": ([vp, vp], C.c_int),
         "ppe_attack_set": ([vp, C.POINTER(AttackCfg)], C.c_int),
         "ppe_attack_clock": ([vp, u64], C.c_int),
         "ppe_attack_tick": ([vp, u64], C.c_int),

@@ -121,6 +121,11 @@ class DeviceSteerOps:
         """Attack monitors are attached to this engine (Engine.attack; ppe_classify_flow then returns PPE_ENOTSUP)."""
         return getattr(self.eng, "attack_attached", None) is not None
 
+    def attack_flow_attached(self) -> bool:
+        """Attack monitors are attached to this engine's flow-table path (Attack.attach_flow): the steered path, which
+        would split the per-port state over the ranks, refuses them."""
+        return getattr(self.eng, "attack_flow_attached", None) is not None
+
     def classify_flow(self, hdr, lens, cfg):
         t = self.torch
         n = lens.numel()
@@ -160,6 +165,11 @@ def steered_classify_flow(ops, dist, hdr, lens, cfg, world: int, rank: int) -> d
     if getattr(ops, "attack_attached", None) and ops.attack_attached():  # and for attached attack monitors
         raise PPEError(f"ppe_classify_flow failed: {abi.PPE_ENOTSUP}: attack monitors are attached "
                        "(ppe_attack_attach); the flow-table path does not support them")
+    # monitors attached to the flow-table path: every rank would keep a share of each port's counts and holds, which is
+    # not the reference's one state per port, and nobody has measured the steered path with them
+    if getattr(ops, "attack_flow_attached", None) and ops.attack_flow_attached():
+        raise PPEError(f"steered ppe_classify_flow failed: {abi.PPE_ENOTSUP}: attack monitors are attached to the "
+                       "flow-table path (ppe_flow_attack_attach); the steered path does not support them")
     perm, counts, send_hdr, send_len = steer_prepare(ops, hdr, lens, cfg, world, rank)
     send_counts = counts.to(torch.int64)
     recv_counts = torch.empty_like(send_counts)

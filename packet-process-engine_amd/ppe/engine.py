@@ -232,11 +232,15 @@ class Engine:
         return ps
 
     # ---- attack monitors (ppe_attack_*, dataplane/src/attack/dp_attack.c) ----
-    def attack(self, cfg: "abi.AttackCfg | None" = None, attach: bool = True) -> "Attack":
+    def attack(self, cfg: "abi.AttackCfg | None" = None, attach: "bool | str" = True) -> "Attack":
         """ppe_attack_create (cfg None: all-zero rules, hold 600 s) and, unless attach is false, ppe_attack_attach: later
-        ppe_classify / ppe_classify_batches launches run the land, SYN-flood and UDP-flood monitors."""
+        ppe_classify / ppe_classify_batches launches run the land, SYN-flood and UDP-flood monitors.  attach="flow":
+        ppe_flow_attack_attach instead: later ppe_classify_flow calls run them, syncount_accum counting the flows SYNs
+        create; the stateless calls then run without monitors."""
         a = Attack(self, cfg)
-        if attach:
+        if attach == "flow":
+            a.attach_flow()
+        elif attach:
             a.attach()
         return a
 
@@ -417,7 +421,8 @@ class PortScan:
 
 class Attack:
     """The attack monitors of one Engine (ppe_attack_create): land, SYN flood, SYN count and UDP flood on the stateless
-    classify path (dataplane/src/attack/dp_attack.c).  Every call goes through libppe_hip.so."""
+    classify path (attach) or on the flow-table path (attach_flow), one of the two at a time
+    (dataplane/src/attack/dp_attack.c).  Every call goes through libppe_hip.so."""
 
     def __init__(self, engine: Engine, cfg: "abi.AttackCfg | None" = None):
         self.eng = engine
@@ -441,11 +446,22 @@ class Attack:
         self.eng._check(self.lib.ppe_attack_attach(self.eng.ctx, None), "ppe_attack_attach")
         self.eng.attack_attached = None
 
+    def attach_flow(self):
+        """ppe_flow_attack_attach: ppe_classify_flow runs the monitors; the engine's stateless calls do not see them."""
+        self.eng._check(self.lib.ppe_flow_attack_attach(self.eng.ctx, self.h), "ppe_flow_attack_attach")
+        self.eng.attack_flow_attached = self
+
+    def detach_flow(self):
+        self.eng._check(self.lib.ppe_flow_attack_attach(self.eng.ctx, None), "ppe_flow_attack_attach")
+        self.eng.attack_flow_attached = None
+
     def close(self):
         if self.h:
-            self.lib.ppe_attack_destroy(self.h)  # (detaches it first)
+            self.lib.ppe_attack_destroy(self.h)  # (detaches it first, from whichever point holds it)
             if getattr(self.eng, "attack_attached", None) is self:
                 self.eng.attack_attached = None
+            if getattr(self.eng, "attack_flow_attached", None) is self:
+                self.eng.attack_flow_attached = None
             self.h = C.c_void_p()
 
     def set(self, cfg: "abi.AttackCfg"):
