@@ -141,6 +141,29 @@ extern uint32_t syn_check;
 extern uint32_t stream_tcp_track_enable;
 extern uint32_t stream_tcp_midstream;
 extern uint32_t stream_tcp_async_oneside;
+/* The port-scan detector behind Decode (PortScan_Detect on every flow miss, flow.c:215-230; the stateless path treats
+ * every packet as one), named as in the reference (dp_portscan.c:9-11, dp_attack.c:25) and read per classify call.
+ * Start values: portscan_able 0 (OFF: the verdicts stay those without the detector; the reference starts with 1),
+ * portscan_action 0 (drop), portscan_exception_freq 50, flood_hold_time 600.  With portscan_able == 1 the first
+ * flush creates the table (PORTSCAN_ITEM_NUM = 100,000 records) and every burst runs the detector in burst order
+ * through ppe_classify_host_ordered (ppe_hip.h); across threads the order is the order in which the flushes take the
+ * engine.  A packet it drops (status PPE_ST_PORTSCAN_DROP) goes to the drop hook without DP_Log_Func (flow.c:216-230
+ * logs nothing), with the fields the TCP / UDP decoders wrote and without PKT_HAS_FLOW / PKT_TO_SERVER.  Setting
+ * portscan_able back to 0 keeps the table and its records, and the verdicts are again those without it.  The land /
+ * flood monitors are not built behind Decode. */
+extern uint32_t portscan_able;
+extern uint32_t portscan_action;
+extern uint32_t portscan_exception_freq;
+extern uint32_t flood_hold_time;
+/* cvmx_get_cycle() and OCT_TIME_SECONDS_SINCE1970 (dp_portscan.c:158-198) for the bursts flushed afterwards, by
+ * value; 1e9 cycles are one second.  Both start at 0.  mbuf->timestamp is what the hold test reads (:145). */
+void DP_PortScan_Clock(uint64_t now_cycles, uint64_t now_seconds);
+/* PortScan_timeout (dp_portscan.c:43-93) at now_cycles; *freed (may be NULL) = records freed.  PPE_OK without a table */
+int  DP_PortScan_Age(uint64_t now_cycles, uint64_t *freed);
+/* the detector's table for ppe_portscan_info / _dump / ppe_format_pkt_stat_ps / ppe_format_fw_config (ppe_hip.h);
+ * NULL before the first flush with portscan_able == 1 and after DP_Acl_Rule_Release */
+struct ppe_portscan_table;
+struct ppe_portscan_table *DP_PortScan_Table(void);
 
 void Decode(mbuf_t *m);
 /* Classify every mbuf the calling thread has queued; returns the number delivered through the output hooks, or a

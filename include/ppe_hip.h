@@ -42,7 +42,8 @@ extern "C" {
  * (ppe_stream_tcp_*, statuses 20-23, ppe_stream_counters_*, ppe_format_tcpstream_stat), off until set; the port-scan
  * detector (ppe_portscan_*, status 24, ppe_format_pkt_stat_ps, ppe_format_fw_config), off until a table is attached;
  * the land / SYN-flood / UDP-flood monitors (ppe_attack_*, statuses 25-28, ppe_format_attack_stat,
- * ppe_format_pkt_stat_atk), off until an object is attached */
+ * ppe_format_pkt_stat_atk), off until an object is attached; ppe_classify_host_ordered and
+ * ppe_portscan_prepass_info */
 #define PPE_ABI_VERSION 8
 
 /* error codes (negative return values) */
@@ -260,6 +261,22 @@ int  ppe_classify_batches(ppe_ctx_t *ctx, const ppe_batch_t *in, const ppe_resul
  * Output pointers are host pointers (NULL to skip).  Blocks until done. */
 int  ppe_classify_host(ppe_ctx_t *ctx, const ppe_batch_t *in, const ppe_result_t *out, const ppe_cfg_t *cfg,
                        uint32_t chunk);
+
+/* ppe_classify_host for a context that may have a port-scan table attached (ppe_portscan_attach).  Same arguments.
+ * The outputs, the counters and the table's records after the call are those of one ppe_classify of the same batch
+ * from device buffers with the same context state (StreamTcp setting included), whatever `chunk` is: the detector is
+ * packet-sequential with a clock that is constant over the call, so chunks of 64 k packets taken as consecutive
+ * batches give the whole batch's record grants (by first appearance), `cycle` stamps and NOMEM.
+ * With the detector on (a table attached, able = 1) every chunk's pre-pass and classify launch go to one internal
+ * stream in chunk order, and so do the H2D / D2H copies (measured faster than leaving them on the staging slots'
+ * streams with an event each way, which PPE_HOST_ORDERED_COPY=1 at ppe_ctx_create selects).  `chunk` is rounded up to a multiple
+ * of 64 and clamped to the table's max_batch rounded down to one (max_batch below 64: PPE_EINVAL); 0 = 1 << 18.
+ * When every buffer is pinned and device-mapped and the batch fits max_batch, the call is one launch, as in
+ * ppe_classify_host.  Without a table, or with able = 0, the call is ppe_classify_host's pipeline: equal outputs for
+ * every layout that call accepts.  With attack monitors attached (ppe_attack_attach) it returns PPE_ENOTSUP before
+ * touching anything.  Blocks until done. */
+int  ppe_classify_host_ordered(ppe_ctx_t *ctx, const ppe_batch_t *in, const ppe_result_t *out, const ppe_cfg_t *cfg,
+                               uint32_t chunk);
 
 /* ACL-only lookup over already-decoded 5-tuples (DP_Acl_Lookup, dataplane/src/flow/flow.c:232).
  * tuple: n × 4 words {sip, dip, sport | dport << 16, proto} — the same layout as ppe_result_t.tuple;
@@ -543,7 +560,11 @@ int  ppe_defrag_info(ppe_defrag_t *d, ppe_defrag_info_t *info);      /* synchron
  * enqueued after it (by value, no synchronisation); rate (oct_cpu_rate) is cycles_per_second.
  * With a table attached and able = 1 every classify call of the context must go through one stream (or be ordered by
  * the caller), and ppe_classify_flow and ppe_classify_host return PPE_ENOTSUP before touching anything (the first:
- * whether a packet is a miss depends on earlier packets' verdicts; the second: its chunks run on several streams).
+ * whether a packet is a miss depends on earlier packets' verdicts; the second: its chunks run on several streams;
+ * ppe_classify_host_ordered is the host-buffer call that runs the detector).
+ * The pre-pass of a batch of at most 2,048 packets is one kernel launch of one workgroup; a larger batch takes the
+ * staged launches (ten, and more sort passes above 2,048 keys).  Both leave the same verdicts, counters and records.
+ * PPE_PS_FUSED=0 in the environment at ppe_portscan_create gives a table that always takes the staged launches.
  * A new context has nothing attached: every output and counter is as without this interface. */
 typedef struct {
     uint32_t able;               /* portscan_able (dp_portscan.c:10); 0/1                                         */
@@ -587,6 +608,9 @@ int  ppe_portscan_age(ppe_portscan_t *ps, uint64_t now_cycles, uint64_t *freed);
 int  ppe_portscan_info(ppe_portscan_t *ps, ppe_portscan_info_t *info);   /* synchronises */
 /* Copy up to `max` records to host (table order); *n = records in use.  Synchronises. */
 int  ppe_portscan_dump(ppe_portscan_t *ps, ppe_portscan_entry_t *entries, uint32_t max, uint32_t *n);
+/* The pre-pass of the last batch enqueued with this table: *kind 1 the one-launch kernel, 0 the staged launches;
+ * *launches the kernel launches it made (0 before the first batch).  Either pointer may be NULL.  No synchronisation. */
+int  ppe_portscan_prepass_info(ppe_portscan_t *ps, uint32_t *kind, uint32_t *launches);
 const char *ppe_portscan_last_error(ppe_portscan_t *ps);
 
 

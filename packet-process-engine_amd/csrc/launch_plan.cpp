@@ -314,6 +314,10 @@ uint32_t ppe_pick_portscan(int flow, int attached, uint32_t able) {
     return (!flow && attached && able == 1u) ? 1u : 0u;  // portscan_able != 1: DECODE_OK at once (dp_portscan.c:238-241)
 }
 
+uint32_t ppe_pick_portscan_prepass(uint32_t n, int fused_allowed) {
+    return (fused_allowed && n >= 1u && n <= PPE_PS_FUSED_CUTOFF) ? 1u : 0u;
+}
+
 uint32_t ppe_pick_attack(int flow, int attached) {
     return (!flow && attached) ? 1u : 0u;  // the monitors sit in the decoders (decode-ipv4.c:141-149, decode-tcp.c:162-173)
 }

@@ -31,6 +31,13 @@ uint32_t syn_check = 1;              /* dataplane/src/flow/flow.c:26 */
 uint32_t stream_tcp_track_enable = 0;
 uint32_t stream_tcp_midstream = 0;
 uint32_t stream_tcp_async_oneside = 0;
+/* The port-scan detector's settings (dataplane/src/attack/dp_portscan.c:9-11, dp_attack.c:25), read per classify call.
+ * The reference starts with portscan_able = 1; this library starts with it OFF, like StreamTcp above: set
+ * portscan_able = 1 for the reference's default behaviour. */
+uint32_t portscan_able = 0;
+uint32_t portscan_action = 0;
+uint32_t portscan_exception_freq = 50;
+uint32_t flood_hold_time = 600;
 PluginModule plugin_modules[PLUGIN_SIZE];
 
 struct ppe_tree_set {
@@ -54,6 +61,10 @@ static pthread_mutex_t g_lock = PTHREAD_MUTEX_INITIALIZER;
  * Decode flush's classify, a rule commit, an ACL lookup, the release — holds g_ctx_lock, always the innermost lock
  * (g_lock and rulelist_mutex may be held around it, never taken inside it). */
 static pthread_mutex_t g_ctx_lock = PTHREAD_MUTEX_INITIALIZER;
+/* the detector's table (created by the first flush with portscan_able == 1, destroyed with the context) and the
+ * clock DP_PortScan_Clock last gave; all under g_ctx_lock */
+static ppe_portscan_t *g_ps = NULL;
+static uint64_t g_ps_cycles = 0, g_ps_seconds = 0;
 static fw_alert fw_log_fun = NULL;
 static ppe_output_fn out_fw = NULL, out_drop = NULL, out_punt = NULL;
 
@@ -164,6 +175,8 @@ void DP_Acl_Rule_Clean(TreeSet **tset, TreeNode **tnode) {
 void DP_Acl_Rule_Release(void) {
     pthread_mutex_lock(&g_lock);
     pthread_mutex_lock(&g_ctx_lock);  /* no flush, commit or lookup is using the context being destroyed */
+    if (g_ps) ppe_portscan_destroy(g_ps);  /* (before its context) */
+    g_ps = NULL;
     if (g_ctx) ppe_ctx_destroy(g_ctx);
     g_ctx = NULL;
     g_published = 0;  /* (a new context numbers its tokens from 1 again) */
@@ -398,8 +411,52 @@ static void fill_mbuf(mbuf_t *m, uint32_t v, uint32_t fhash, int32_t hit, const 
     }
     /* FlowHandlePacket found or created the flow (ACL passed): flow.c:294-307.  Every packet of the stateless path
      * is its flow's first, and FlowAdd orients the flow as that packet, so the direction is to-server.
-     * StreamTcp runs after that (flow.c:311-320), so a packet it drops carries the flags too. */
-    if (st == PPE_ST_ACL_FW || st >= PPE_ST_STREAM_RST_NO_SESSION) m->flags |= PKT_TO_SERVER | PKT_HAS_FLOW;
+     * StreamTcp runs after that (flow.c:311-320), so a packet it drops carries the flags too.  A packet the port-scan
+     * detector dropped has no flow: FlowGetFlowFromHash returned NULL before FlowAdd (flow.c:216-230). */
+    if (st == PPE_ST_ACL_FW || (st >= PPE_ST_STREAM_RST_NO_SESSION && st <= PPE_ST_STREAM_MIDSTREAM_OFF))
+        m->flags |= PKT_TO_SERVER | PKT_HAS_FLOW;
+}
+
+/* PortScan_Detect behind Decode (flow.c:215-230), caller holds g_ctx_lock and g_ctx is set: the table on first use
+ * (PORTSCAN_ITEM_NUM records; max_batch at least this burst: a later, larger burst goes through it in chunks), then
+ * the globals and the clock by value for this burst, attached. */
+static int portscan_prepare_locked(uint32_t n) {
+    if (!g_ps) {
+        ppe_portscan_cfg_t c = {1u, 0u, 50u, 600u, 100000u, 0u, 1000000000ull, 0u};
+        c.max_batch = ((n > 4096u ? n : 4096u) + 63u) & ~63u;
+        const int rc = ppe_portscan_create(g_ctx, &c, &g_ps);
+        if (rc != PPE_OK) {
+            g_ps = NULL;
+            return rc;
+        }
+    }
+    ppe_portscan_cfg_t v = {1u, portscan_action ? 1u : 0u, portscan_exception_freq, flood_hold_time, 0u, 0u, 0u, 0u};
+    int rc = ppe_portscan_set(g_ps, &v);
+    if (rc == PPE_OK) rc = ppe_portscan_clock(g_ps, g_ps_cycles, g_ps_seconds);
+    if (rc == PPE_OK) rc = ppe_portscan_attach(g_ctx, g_ps);
+    return rc;
+}
+
+void DP_PortScan_Clock(uint64_t now_cycles, uint64_t now_seconds) {
+    pthread_mutex_lock(&g_ctx_lock);
+    g_ps_cycles = now_cycles;
+    g_ps_seconds = now_seconds;
+    pthread_mutex_unlock(&g_ctx_lock);
+}
+
+int DP_PortScan_Age(uint64_t now_cycles, uint64_t *freed) {
+    if (freed) *freed = 0;
+    pthread_mutex_lock(&g_ctx_lock);
+    const int rc = g_ps ? ppe_portscan_age(g_ps, now_cycles, freed) : PPE_OK;
+    pthread_mutex_unlock(&g_ctx_lock);
+    return rc;
+}
+
+ppe_portscan_t *DP_PortScan_Table(void) {
+    pthread_mutex_lock(&g_ctx_lock);
+    ppe_portscan_t *t = g_ps;
+    pthread_mutex_unlock(&g_ctx_lock);
+    return t;
 }
 
 /* Classify `n` mbufs on the GPU (serialised) and fill their parse fields; returns PPE_OK or a PPE_E* code. */
@@ -432,7 +489,13 @@ static int classify_mbufs(mbuf_t **mb, uint32_t n) {
         pthread_mutex_lock(&g_ctx_lock);
         sync_running_locked();
         rc = g_ctx ? ppe_stream_tcp_set(g_ctx, &stcp) : PPE_ENODEV;
-        if (rc == PPE_OK) rc = ppe_classify_host(g_ctx, &b, &r, &cfg, 0);
+        if (rc == PPE_OK && portscan_able == 1u) {  /* (dp_portscan.c:238: any other value is off) */
+            rc = portscan_prepare_locked(n);
+            if (rc == PPE_OK) rc = ppe_classify_host_ordered(g_ctx, &b, &r, &cfg, 0);
+        } else if (rc == PPE_OK) {
+            if (g_ps) rc = ppe_portscan_attach(g_ctx, NULL);  /* the table keeps its records while off */
+            if (rc == PPE_OK) rc = ppe_classify_host(g_ctx, &b, &r, &cfg, 0);
+        }
         pthread_mutex_unlock(&g_ctx_lock);
         if (rc == PPE_OK)
             for (uint32_t i = 0; i < n; i++) fill_mbuf(mb[i], verdict[i], fh[i], hit[i], tuple + 4 * (size_t)i);

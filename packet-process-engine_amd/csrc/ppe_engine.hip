@@ -124,6 +124,8 @@ struct ppe_portscan_table {
     unsigned long long *skey = nullptr, *cmask = nullptr, *mask = nullptr;
     uint8_t *res = nullptr;
     size_t mask_cap = 0;          // words of `mask`: the drop masks of the batches of one launch
+    int fused_ok = 1;             // PPE_PS_FUSED at creation: 0 = every batch takes the staged launches
+    uint32_t last_kind = 0, last_launches = 0;  // ppe_portscan_prepass_info: the last batch's pre-pass
     char err[256] = {0};
 };
 
@@ -173,6 +175,14 @@ struct ppe_ctx {
     size_t ev_used = 0;
     // host pipeline
     HostStage hs[kHostStreams];
+    // ppe_classify_host_ordered: the one stream every chunk's pre-pass and classify launch goes to, and per staging
+    // slot the events behind its upload and its launch
+    hipStream_t host_cs = nullptr;
+    hipEvent_t host_ev[kHostStreams][2] = {};
+    // PPE_HOST_ORDERED_COPY at context creation: 0 the copies on host_cs too, 1 on the slots' streams with an event each
+    // way.  One stream is faster at every size measured (pageable, 64 packets 72 vs 95 us, 262,144 in chunks of 16,384
+    // 2.97 vs 3.41 ms, tools/ab_portscan_small.py): the detector's launches leave no room to overlap a copy with
+    int host_ordered_copy = 0;
     // device-batch pipeline (ppe_classify_batches): consecutive batches alternate over these streams
     hipStream_t pipe[kPipeStreams] = {};
     hipEvent_t pipe_ev[kPipeStreams + 1] = {};
@@ -614,6 +624,13 @@ int ps_prepass(ppe_ctx *c, const ppe_batch_t *in, uint32_t nb, const ppe_cfg_t *
             a.atk_ports = k < c->atk->h_ports.size() ? c->atk->h_ports[k] : nullptr;
         }
         off += (n + 63u) / 64u;
+        if (ppe_pick_portscan_prepass(n, t->fused_ok)) {  // a small batch: every phase in one launch of one workgroup
+            PSCHK(t, ppe_launch_portscan(PPE_PS_K_FUSED, &a, s));
+            t->last_kind = 1u;
+            t->last_launches = 1u;
+            continue;
+        }
+        uint32_t launches = 10u;  // pre, post
         static const int pre[] = {PPE_PS_K_FIND, PPE_PS_K_CREATORS, PPE_PS_K_SCAN, PPE_PS_K_GRANT, PPE_PS_K_KEYS,
                                   PPE_PS_K_SORT_LDS};
         for (int k : pre) PSCHK(t, ppe_launch_portscan(k, &a, s));
@@ -622,11 +639,15 @@ int ps_prepass(ppe_ctx *c, const ppe_batch_t *in, uint32_t nb, const ppe_cfg_t *
             for (uint32_t j = k >> 1; j >= PPE_PS_SORT_BLOCK; j >>= 1) {
                 a.sort_j = j;
                 PSCHK(t, ppe_launch_portscan(PPE_PS_K_SORT_GLOBAL, &a, s));
+                ++launches;
             }
             PSCHK(t, ppe_launch_portscan(PPE_PS_K_SORT_MERGE_LDS, &a, s));
+            ++launches;
         }
         static const int post[] = {PPE_PS_K_HEADS, PPE_PS_K_MEMBERS, PPE_PS_K_WALK, PPE_PS_K_MASK};
         for (int k : post) PSCHK(t, ppe_launch_portscan(k, &a, s));
+        t->last_kind = 0u;
+        t->last_launches = launches;
     }
     return PPE_OK;
 }
@@ -784,6 +805,7 @@ int ppe_ctx_create(int device, ppe_ctx_t **out) {
     c->tune = default_tuning();
     c->max_groups = (uint32_t)std::max(1, env_int("PPE_GROUPS", 8));
     c->pipe_mode = env_int("PPE_PIPE_MODE", 1);
+    c->host_ordered_copy = env_int("PPE_HOST_ORDERED_COPY", 0) != 0;
     const size_t cs_bytes = (size_t)kSlotSets * c->max_grid * PPE_CSLOT_WORDS * sizeof(unsigned long long);
     int rc = PPE_OK;
     if (hipMalloc(&c->d_cslots, cs_bytes) != hipSuccess || hipMemset(c->d_cslots, 0, cs_bytes) != hipSuccess)
@@ -852,6 +874,10 @@ int ppe_ctx_destroy(ppe_ctx_t *c) {
     if (c->lk.s) (void)hipStreamDestroy(c->lk.s);
     if (c->lk.h) (void)hipHostFree(c->lk.h);
     if (c->d_steer) (void)hipFree(c->d_steer);
+    if (c->host_cs) (void)hipStreamDestroy(c->host_cs);
+    for (auto &pair : c->host_ev)
+        for (hipEvent_t e : pair)
+            if (e) (void)hipEventDestroy(e);
     for (auto &h : c->hs) {
         if (h.s) (void)hipStreamDestroy(h.s);
         (void)hipFree(h.hdr);
@@ -1040,19 +1066,20 @@ static const void *mapped_host(const void *p) {
     return (const char *)at.devicePointer + ((const char *)p - (const char *)at.hostPointer);
 }
 
-int ppe_classify_host(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *out, const ppe_cfg_t *cfg,
-                      uint32_t chunk) {
-    if (!c || !out) return PPE_EINVAL;
-    // the chunks of the staged path run on several streams; the detector needs the packets in order on one
-    if (c->ps) return fail(c, PPE_ENOTSUP, "ppe_classify_host with a port-scan table attached is not supported");
-    // the same for the attack monitors: their hold and their clock follow the order of the launches on one stream
-    if (c->atk) return fail(c, PPE_ENOTSUP, "ppe_classify_host with attack monitors attached is not supported");
+// ppe_classify_host (ordered false: the chunks' launches on the staging slots' streams) and
+// ppe_classify_host_ordered with the detector on (ordered: every chunk's pre-pass and classify launch on c->host_cs, in
+// chunk order; the copies go to host_cs too, or stay on the slots' streams with an event each way)
+static int classify_host_run(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *out, const ppe_cfg_t *cfg,
+                             uint32_t chunk, bool ordered) {
     int rc = check_batch(c, in, cfg);
     if (rc != PPE_OK || in->n == 0) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     // Zero-copy: when every buffer is pinned and device-mapped, the kernel reads the windows and writes the results
     // across PCIe itself (C1: 822 vs 628 Mpps for the staged copies below, tools/host_zero_copy.py)
-    if (env_int("PPE_HOST_ZEROCOPY", 1)) {
+    const uint32_t ps_max = ordered ? c->ps->cfg.max_batch : 0u;  // the detector takes max_batch packets per launch
+    if (ordered && ps_max < 64u)
+        return fail(c, PPE_EINVAL, "ppe_classify_host_ordered: the port-scan table's max_batch is below one tile");
+    if (env_int("PPE_HOST_ZEROCOPY", 1) && (!ordered || in->n <= ps_max)) {
         ppe_batch_t b = *in;
         ppe_result_t r = *out;
         bool ok = (b.hdr = (const uint8_t *)mapped_host(in->hdr)) && (b.len = (const uint32_t *)mapped_host(in->len));
@@ -1073,6 +1100,14 @@ int ppe_classify_host(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *o
     if (chunk == 0) chunk = 1u << 18;
     chunk = (chunk + 63u) & ~63u;
     chunk = std::min(chunk, (in->n + 63u) & ~63u);
+    if (ordered) {
+        chunk = std::min(chunk, ps_max & ~63u);
+        if (!c->host_cs) HIPCHK(c, hipStreamCreateWithFlags(&c->host_cs, hipStreamNonBlocking));
+        if (c->host_ordered_copy)
+            for (auto &pair : c->host_ev)
+                for (hipEvent_t &e : pair)
+                    if (!e) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
     for (auto &h : c->hs) {
         if (!h.s) HIPCHK(c, hipStreamCreateWithFlags(&h.s, hipStreamNonBlocking));
         if (h.cap < chunk || h.stride != in->stride) {
@@ -1096,10 +1131,13 @@ int ppe_classify_host(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *o
     const hipMemcpyKind h2d = hipMemcpyHostToDevice, d2h = hipMemcpyDeviceToHost;
     for (uint32_t base = 0, i = 0; base < in->n; base += chunk, ++i) {
         HostStage &h = c->hs[i % kHostStreams];
+        hipEvent_t *ev = c->host_ev[i % kHostStreams];
+        const hipStream_t ls = ordered ? c->host_cs : h.s;                           // the launches
+        const hipStream_t xs = (ordered && !c->host_ordered_copy) ? c->host_cs : h.s;  // the copies
         const uint32_t m = std::min(chunk, in->n - base);
-        HIPCHK(c, hipMemcpyAsync(h.hdr, in->hdr + (size_t)base * in->stride, (size_t)m * in->stride, h2d, h.s));
-        HIPCHK(c, hipMemcpyAsync(h.len, in->len + base, (size_t)m * 4, h2d, h.s));
-        if (in->ts) HIPCHK(c, hipMemcpyAsync(h.ts, in->ts + base, (size_t)m * 8, h2d, h.s));
+        HIPCHK(c, hipMemcpyAsync(h.hdr, in->hdr + (size_t)base * in->stride, (size_t)m * in->stride, h2d, xs));
+        HIPCHK(c, hipMemcpyAsync(h.len, in->len + base, (size_t)m * 4, h2d, xs));
+        if (in->ts) HIPCHK(c, hipMemcpyAsync(h.ts, in->ts + base, (size_t)m * 8, h2d, xs));
         ppe_batch_t b = {h.hdr, h.len, in->ts ? h.ts : nullptr, m, in->stride};
         ppe_result_t r;
         r.verdict = out->verdict ? h.verdict : nullptr;
@@ -1112,23 +1150,53 @@ int ppe_classify_host(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *o
         r.tuple = out->tuple ? h.tuple : nullptr;
         r.part8 = out->part8 ? (uint8_t *)h.fw : nullptr;  // (part8 excludes fw_idx: the staging list is free)
         r.packed = out->packed ? (uint64_t *)h.tuple : nullptr;
-        rc = launch(c, &b, &r, 1, cfg, h.s, 1 + (int)(i % kHostStreams), base);
+        if (xs != ls) {  // the launch after the slot's upload, its download after the launch
+            HIPCHK(c, hipEventRecord(ev[0], xs));
+            HIPCHK(c, hipStreamWaitEvent(ls, ev[0], 0));
+        }
+        // (launches that follow each other on one stream share one counter slot set)
+        rc = launch(c, &b, &r, 1, cfg, ls, ordered ? 1 : 1 + (int)(i % kHostStreams), base);
         if (rc != PPE_OK) return rc;
-        if (out->verdict) HIPCHK(c, hipMemcpyAsync(out->verdict + base, h.verdict, (size_t)m * 4, d2h, h.s));
-        if (out->flow_hash) HIPCHK(c, hipMemcpyAsync(out->flow_hash + base, h.fhash, (size_t)m * 4, d2h, h.s));
-        if (out->acl_hit) HIPCHK(c, hipMemcpyAsync(out->acl_hit + base, h.hit, (size_t)m * 4, d2h, h.s));
-        if (out->tuple) HIPCHK(c, hipMemcpyAsync(out->tuple + (size_t)base * 4, h.tuple, (size_t)m * 16, d2h, h.s));
+        if (xs != ls) {
+            HIPCHK(c, hipEventRecord(ev[1], ls));
+            HIPCHK(c, hipStreamWaitEvent(xs, ev[1], 0));
+        }
+        if (out->verdict) HIPCHK(c, hipMemcpyAsync(out->verdict + base, h.verdict, (size_t)m * 4, d2h, xs));
+        if (out->flow_hash) HIPCHK(c, hipMemcpyAsync(out->flow_hash + base, h.fhash, (size_t)m * 4, d2h, xs));
+        if (out->acl_hit) HIPCHK(c, hipMemcpyAsync(out->acl_hit + base, h.hit, (size_t)m * 4, d2h, xs));
+        if (out->tuple) HIPCHK(c, hipMemcpyAsync(out->tuple + (size_t)base * 4, h.tuple, (size_t)m * 16, d2h, xs));
         if (out->tile_cnt)
-            HIPCHK(c, hipMemcpyAsync(out->tile_cnt + base / 64, h.tcnt, (size_t)((m + 63) / 64) * 4, d2h, h.s));
+            HIPCHK(c, hipMemcpyAsync(out->tile_cnt + base / 64, h.tcnt, (size_t)((m + 63) / 64) * 4, d2h, xs));
         // compacted indices carry the batch index (idx_base); chunk is a multiple of 64, so tiles line up
-        if (out->fw_idx) HIPCHK(c, hipMemcpyAsync(out->fw_idx + base, h.fw, (size_t)m * 4, d2h, h.s));
+        if (out->fw_idx) HIPCHK(c, hipMemcpyAsync(out->fw_idx + base, h.fw, (size_t)m * 4, d2h, xs));
         if (out->drop_idx && !part)
-            HIPCHK(c, hipMemcpyAsync(out->drop_idx + base, h.drop, (size_t)m * 4, d2h, h.s));
-        if (out->part8) HIPCHK(c, hipMemcpyAsync(out->part8 + base, h.fw, (size_t)m, d2h, h.s));
-        if (out->packed) HIPCHK(c, hipMemcpyAsync(out->packed + base, h.tuple, (size_t)m * 8, d2h, h.s));
+            HIPCHK(c, hipMemcpyAsync(out->drop_idx + base, h.drop, (size_t)m * 4, d2h, xs));
+        if (out->part8) HIPCHK(c, hipMemcpyAsync(out->part8 + base, h.fw, (size_t)m, d2h, xs));
+        if (out->packed) HIPCHK(c, hipMemcpyAsync(out->packed + base, h.tuple, (size_t)m * 8, d2h, xs));
     }
+    if (ordered) HIPCHK(c, hipStreamSynchronize(c->host_cs));
     for (auto &h : c->hs) HIPCHK(c, hipStreamSynchronize(h.s));
     return PPE_OK;
+}
+
+int ppe_classify_host(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *out, const ppe_cfg_t *cfg,
+                      uint32_t chunk) {
+    if (!c || !out) return PPE_EINVAL;
+    // the chunks of the staged path run on several streams; the detector needs the packets in order on one
+    if (c->ps) return fail(c, PPE_ENOTSUP, "ppe_classify_host with a port-scan table attached is not supported");
+    // the same for the attack monitors: their hold and their clock follow the order of the launches on one stream
+    if (c->atk) return fail(c, PPE_ENOTSUP, "ppe_classify_host with attack monitors attached is not supported");
+    return classify_host_run(c, in, out, cfg, chunk, false);
+}
+
+int ppe_classify_host_ordered(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *out, const ppe_cfg_t *cfg,
+                              uint32_t chunk) {
+    if (!c || !out) return PPE_EINVAL;
+    // the monitors' per-batch port arrays do not map onto chunks
+    if (c->atk) return fail(c, PPE_ENOTSUP, "ppe_classify_host_ordered with attack monitors attached is not supported");
+    // without the detector (no table, or portscan_able 0) the chunks are independent: ppe_classify_host's pipeline
+    const bool psc = ppe_pick_portscan(0, c->ps != nullptr, c->ps ? c->ps->cfg.able : 0u) != 0u;
+    return classify_host_run(c, in, out, cfg, chunk, psc);
 }
 
 int ppe_acl_lookup(ppe_ctx_t *c, const ppe_tuples_t *in, int32_t *hit, uint32_t *action, uint64_t now_seconds,
@@ -1336,6 +1404,7 @@ int ppe_portscan_create(ppe_ctx_t *c, const ppe_portscan_cfg_t *cfg, ppe_portsca
     ppe_portscan_table *t = new ppe_portscan_table;
     t->ctx = c;
     t->cfg = v;
+    t->fused_ok = env_int("PPE_PS_FUSED", 1) != 0;  // A/B switch: 0 keeps every batch on the staged launches
     uint32_t ns = 1024;
     while (ns < 2u * (v.capacity + v.max_batch)) ns <<= 1;
     t->nslots = ns;
@@ -1454,6 +1523,13 @@ int ppe_portscan_dump(ppe_portscan_t *t, ppe_portscan_entry_t *entries, uint32_t
         ++cnt;
     }
     *n = cnt;
+    return PPE_OK;
+}
+
+int ppe_portscan_prepass_info(ppe_portscan_t *t, uint32_t *kind, uint32_t *launches) {
+    if (!t) return PPE_EINVAL;
+    if (kind) *kind = t->last_kind;
+    if (launches) *launches = t->last_launches;
     return PPE_OK;
 }
 

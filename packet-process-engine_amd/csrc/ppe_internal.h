@@ -318,7 +318,10 @@ struct ppe_ps_kargs {
 };
 enum { PPE_PS_K_FIND = 0, PPE_PS_K_CREATORS, PPE_PS_K_SCAN, PPE_PS_K_GRANT, PPE_PS_K_KEYS, PPE_PS_K_SORT_LDS,
        PPE_PS_K_SORT_MERGE_LDS, PPE_PS_K_SORT_GLOBAL, PPE_PS_K_HEADS, PPE_PS_K_MEMBERS, PPE_PS_K_WALK, PPE_PS_K_MASK,
-       PPE_PS_K_REBUILD };
+       PPE_PS_K_REBUILD, PPE_PS_K_FUSED /* find .. mask in one launch of one workgroup, n <= PPE_PS_SORT_BLOCK */ };
+/* largest batch the one-launch pre-pass takes (ppe_pick_portscan_prepass).  tools/ab_portscan_small.py measures it
+ * against the staged launches at 1 .. 2,048 packets */
+#define PPE_PS_FUSED_CUTOFF PPE_PS_SORT_BLOCK
 
 /* flow-hash steering across GPUs (ppe_steer_partition / ppe_gather_rows / ppe_scatter_rows) */
 #define PPE_STEER_MAX_WORLD 16
@@ -413,6 +416,9 @@ uint32_t ppe_pick_groups(uint32_t nbatch, uint32_t max_groups);
 /* 1: the launch takes the kernels with the port-scan drop mask (PSC): a stateless launch of a context with a table
  * attached whose detector is enabled (portscan_able == 1, dp_portscan.c:238) */
 uint32_t ppe_pick_portscan(int flow, int attached, uint32_t able);
+/* the pre-pass of a batch of n packets: 1 the one-launch kernel (PPE_PS_K_FUSED) for 1 <= n <= PPE_PS_FUSED_CUTOFF
+ * when the table allows it (fused_allowed: not created under PPE_PS_FUSED=0), else 0, the staged launches */
+uint32_t ppe_pick_portscan_prepass(uint32_t n, int fused_allowed);
 /* 1: the launch takes the kernels with the attack monitors (ATK): a stateless launch of a context with an object
  * attached (ppe_attack_attach), and no other launch */
 uint32_t ppe_pick_attack(int flow, int attached);

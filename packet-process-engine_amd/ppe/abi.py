@@ -325,7 +325,7 @@ TUPLE_OPT_PAST = 1 << 15  # include/ppe_hip.h PPE_TUPLE_OPT_PAST (tuple word 3)
 EXPORTS = [
     # ppe_hip.h
     "ppe_abi_version", "ppe_ctx_create", "ppe_ctx_destroy", "ppe_ctx_device", "ppe_rules_commit", "ppe_rules_stage", "ppe_rules_publish", "ppe_classify",
-    "ppe_classify_batches", "ppe_classify_host", "ppe_acl_lookup", "ppe_acl_lookup_host", "ppe_dev_alloc", "ppe_dev_free",
+    "ppe_classify_batches", "ppe_classify_host", "ppe_classify_host_ordered", "ppe_acl_lookup", "ppe_acl_lookup_host", "ppe_dev_alloc", "ppe_dev_free",
     "ppe_host_alloc", "ppe_host_free", "ppe_memcpy_h2d", "ppe_memcpy_d2h", "ppe_memset_d", "ppe_sync",
     "ppe_counters_read", "ppe_counters_clear", "ppe_timing_enable", "ppe_timing_read", "ppe_acl_image",
     "ppe_launch_info", "ppe_last_error", "ppe_acl_build_image", "ppe_acl_free_image", "ppe_set_tuning",
@@ -338,19 +338,20 @@ EXPORTS = [
     "ppe_stream_tcp_set", "ppe_stream_tcp_get", "ppe_stream_counters_read", "ppe_stream_counters_clear",
     "ppe_format_tcpstream_stat",
     "ppe_portscan_create", "ppe_portscan_destroy", "ppe_portscan_attach", "ppe_portscan_clock", "ppe_portscan_set",
-    "ppe_portscan_age", "ppe_portscan_info", "ppe_portscan_dump", "ppe_portscan_last_error",
+    "ppe_portscan_age", "ppe_portscan_info", "ppe_portscan_dump", "ppe_portscan_last_error", "ppe_portscan_prepass_info",
     "ppe_format_pkt_stat_ps", "ppe_format_fw_config",
     "ppe_attack_create", "ppe_attack_destroy", "ppe_attack_attach", "ppe_flow_attack_attach", "ppe_attack_set", "ppe_attack_clock",
     "ppe_attack_tick", "ppe_attack_ports", "ppe_attack_info", "ppe_attack_clear_stat", "ppe_attack_last_error",
     "ppe_format_attack_stat", "ppe_format_pkt_stat_atk",
     # csrc/ppe_internal.h: the host-only launch planner (internal helpers, not part of the public headers)
-    "ppe_plan_image", "ppe_pick_groups", "ppe_pick_portscan", "ppe_pick_attack", "ppe_pick_attack_flow",
+    "ppe_plan_image", "ppe_pick_groups", "ppe_pick_portscan", "ppe_pick_portscan_prepass", "ppe_pick_attack", "ppe_pick_attack_flow",
     # ppe_acl.h
     "ppe_rule_list_init", "ppe_rule_list_free", "Rule_add", "Rule_del_by_id", "Rule_del_all",
     "Rule_duplicate_check", "Rule_Load_Line", "ppe_rule_load_file", "DP_Acl_Rule_Init", "DP_Acl_Load_Rule",
     "DP_Acl_Rule_Clean", "DP_Acl_Rule_Release", "DP_Acl_Rule_Commit",
     # ppe_decode.h
-    "ppe_set_output_hooks", "Decode", "Decode_Flush", "Decode_Set_Burst", "DP_Acl_Lookup_Burst", "DP_Acl_Lookup",
+    "ppe_set_output_hooks", "Decode", "Decode_Flush", "Decode_Set_Burst", "DP_PortScan_Clock", "DP_PortScan_Age",
+    "DP_PortScan_Table", "DP_Acl_Lookup_Burst", "DP_Acl_Lookup",
     "reg_fw_alert", "DP_Log_Func", "ppe_compat_ctx",
 ]
 EXPORTED_DATA = ["rule_list", "dp_acl_action_default", "gWstDepth", "gAvgDepth", "gChildCount", "gNumTreeNode",
@@ -398,6 +399,7 @@ def _open(p: Path, mode, strict: bool = True) -> C.CDLL:
         "ppe_rules_publish": ([vp, C.c_uint64], C.c_int),
         "ppe_classify": ([vp, C.POINTER(Batch), C.POINTER(Result), C.POINTER(Cfg), vp], C.c_int),
         "ppe_classify_host": ([vp, C.POINTER(Batch), C.POINTER(Result), C.POINTER(Cfg), u32], C.c_int),
+        "ppe_classify_host_ordered": ([vp, C.POINTER(Batch), C.POINTER(Result), C.POINTER(Cfg), u32], C.c_int),
         "ppe_classify_batches": ([vp, C.POINTER(Batch), C.POINTER(Result), u32, C.POINTER(Cfg), vp], C.c_int),
         "ppe_acl_lookup": ([vp, C.POINTER(Tuples), vp, vp, u64, vp], C.c_int),
         "ppe_acl_lookup_host": ([vp, C.POINTER(Tuples), vp, vp, u64], C.c_int),
@@ -457,12 +459,14 @@ def _open(p: Path, mode, strict: bool = True) -> C.CDLL:
         "ppe_portscan_info": ([vp, C.POINTER(PortScanInfo)], C.c_int),
         "ppe_portscan_dump": ([vp, vp, u32, C.POINTER(u32)], C.c_int),
         "ppe_portscan_last_error": ([vp], C.c_char_p),
+        "ppe_portscan_prepass_info": ([vp, C.POINTER(u32), C.POINTER(u32)], C.c_int),
         "ppe_format_pkt_stat_ps": ([C.POINTER(Counters), C.POINTER(DefragInfo), C.c_int, C.POINTER(PortScanInfo),
                                     C.c_char_p, C.c_size_t], C.c_int),
         "ppe_format_fw_config": ([C.POINTER(PortScanCfg), C.c_char_p, C.c_size_t], C.c_int),
         "ppe_plan_image": ([vp, u32, C.POINTER(Tuning), C.c_int, C.POINTER(Plan)], C.c_int),
         "ppe_pick_groups": ([u32, u32], u32),
         "ppe_pick_portscan": ([C.c_int, C.c_int, u32], u32),
+        "ppe_pick_portscan_prepass": ([u32, C.c_int], u32),
         "ppe_pick_attack": ([C.c_int, C.c_int], u32),
         "ppe_pick_attack_flow": ([C.c_int, C.c_int], u32),
         "ppe_attack_create": ([vp, C.POINTER(AttackCfg), C.POINTER(vp)], C.c_int),
@@ -493,6 +497,9 @@ def _open(p: Path, mode, strict: bool = True) -> C.CDLL:
         "Decode": ([vp], None),
         "Decode_Flush": ([], C.c_int),
         "Decode_Set_Burst": ([u32], None),
+        "DP_PortScan_Clock": ([u64, u64], None),
+        "DP_PortScan_Age": ([u64, C.POINTER(u64)], C.c_int),
+        "DP_PortScan_Table": ([], vp),
         "DP_Acl_Lookup": ([vp], C.c_int),
         "DP_Acl_Lookup_Burst": ([vp, u32, vp], C.c_int),
     }

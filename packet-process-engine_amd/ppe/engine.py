@@ -103,8 +103,9 @@ class Engine:
 
     def classify_host(self, hdr: np.ndarray, lens: np.ndarray, ts: np.ndarray | None = None,
                       cfg: abi.Cfg | None = None, chunk: int = 0, outputs=("verdict", "flow_hash", "acl_hit"),
-                      ) -> dict:
-        """Host-buffer form (ppe_classify_host: pipelined H2D → classify → D2H).  hdr: (n, stride) uint8."""
+                      ordered: bool = False) -> dict:
+        """Host-buffer form (ppe_classify_host: pipelined H2D → classify → D2H).  hdr: (n, stride) uint8.
+        ordered: ppe_classify_host_ordered, which runs an attached port-scan table's detector (classify_host_ordered)."""
         hdr = np.ascontiguousarray(hdr, dtype=np.uint8)
         lens = np.ascontiguousarray(lens, dtype=np.uint32)
         n, stride = hdr.shape
@@ -131,9 +132,17 @@ class Engine:
         g = lambda k: res[k].ctypes.data if k in res else None  # noqa: E731
         fw, dr = (g("part_idx"), g("part_idx")) if "part_idx" in res else (g("fw_idx"), g("drop_idx"))
         r = abi.Result(g("verdict"), g("flow_hash"), g("acl_hit"), fw, dr, g("tile_cnt"), g("tuple"))
-        rc = self.lib.ppe_classify_host(self.ctx, C.byref(b), C.byref(r), C.byref(cfg or self.cfg()), int(chunk))
-        self._check(rc, "ppe_classify_host")
+        name = "ppe_classify_host_ordered" if ordered else "ppe_classify_host"
+        rc = getattr(self.lib, name)(self.ctx, C.byref(b), C.byref(r), C.byref(cfg or self.cfg()), int(chunk))
+        self._check(rc, name)
         return res
+
+    def classify_host_ordered(self, hdr: np.ndarray, lens: np.ndarray, ts: np.ndarray | None = None,
+                              cfg: abi.Cfg | None = None, chunk: int = 0,
+                              outputs=("verdict", "flow_hash", "acl_hit")) -> dict:
+        """ppe_classify_host_ordered: classify_host whose chunks go through one stream in order, so an attached
+        port-scan table gives one ppe_classify's verdicts, counters and records whatever `chunk` is."""
+        return self.classify_host(hdr, lens, ts, cfg, chunk, outputs, ordered=True)
 
     # ---- flow table (ppe_flow_*, dataplane/src/flow/flow.c) ----
     def flow_create(self, capacity: int = 0, max_batch: int = 0):
@@ -404,6 +413,13 @@ class PortScan:
         freed = C.c_uint64(0)
         self._check(self.lib.ppe_portscan_age(self.h, int(now_cycles), C.byref(freed)), "ppe_portscan_age")
         return freed.value
+
+    def prepass_info(self) -> tuple:
+        """(kind, launches) of the last batch's pre-pass: kind 1 the one-launch kernel, 0 the staged launches."""
+        kind, launches = C.c_uint32(0), C.c_uint32(0)
+        self._check(self.lib.ppe_portscan_prepass_info(self.h, C.byref(kind), C.byref(launches)),
+                    "ppe_portscan_prepass_info")
+        return kind.value, launches.value
 
     def info(self) -> dict:
         i = abi.PortScanInfo()
