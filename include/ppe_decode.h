@@ -165,6 +165,30 @@ int  DP_PortScan_Age(uint64_t now_cycles, uint64_t *freed);
 struct ppe_portscan_table;
 struct ppe_portscan_table *DP_PortScan_Table(void);
 
+/* The flow table behind Decode (FlowHandlePacket with FlowGetFlowFromHash, flow.c:181-310), read per classify call.
+ * Start values: flow_able 0 (OFF: Decode is the stateless path, every packet its flow's first; the reference has no
+ * such switch, its Decode always goes through the table), flow_item_num 100000 (MEM_POOL_FLOW_NODE_NUM), read when
+ * the table is created.  With flow_able == 1 the first flush creates the context's table (flow_item_num flows) and
+ * every burst goes through ppe_classify_flow_host (ppe_hip.h) in burst order, a burst larger than the first in
+ * chunks; across threads the order is the order in which the flushes take the engine.  Then a packet whose flow exists
+ * is forwarded without an ACL lookup (ppe_acl_hit == -1), replies carry PKT_TO_CLIENT | PKT_HAS_FLOW, the creating
+ * direction PKT_TO_SERVER | PKT_HAS_FLOW, and a packet without a flow (ACL drop, FLOW_TCP_NO_SYN_FIRST, or
+ * PPE_ST_FLOW_NOMEM when the pool is empty, which goes to the drop hook without DP_Log_Func, flow.c:124-129) carries
+ * neither.  There is no host flow object: m->flow stays as it was.  The table is read through the shim's context:
+ * ppe_flow_info / ppe_flow_dump / ppe_format_flow_stat on ppe_compat_ctx().  Setting flow_able back to 0 keeps the
+ * table and its flows; DP_Acl_Rule_Release destroys it with the context.
+ * flow_able == 1 together with portscan_able == 1 or stream_tcp_track_enable is not built (the detector on flow misses
+ * only; the TCP session machine): the flush fails with PPE_ENOTSUP before any state changes and every mbuf of the
+ * burst goes to the drop hook, as for any classify step that cannot run. */
+extern uint32_t flow_able;
+extern uint32_t flow_item_num;
+/* FLOW_UPDATE_TIMESTAMP's clock (seconds) for the bursts flushed afterwards, by value.  Starts at 0; with
+ * flow_able == 0 the classify calls keep now_seconds = 0. */
+void DP_Flow_Clock(uint64_t now_seconds);
+/* FlowAgeTimeoutCB (flow.c:391-467) at now_seconds with FLOW_MAX_TIMEOUT = 20: flows idle for more than 20 s are
+ * deleted; *deleted (may be NULL) = their number.  PPE_OK with 0 deleted without a table. */
+int  DP_Flow_Age(uint64_t now_seconds, uint64_t *deleted);
+
 void Decode(mbuf_t *m);
 /* Classify every mbuf the calling thread has queued; returns the number delivered through the output hooks, or a
  * negative PPE_E* code when the GPU step failed, in which case every queued mbuf was handed to the drop hook (the

@@ -43,7 +43,7 @@ extern "C" {
  * detector (ppe_portscan_*, status 24, ppe_format_pkt_stat_ps, ppe_format_fw_config), off until a table is attached;
  * the land / SYN-flood / UDP-flood monitors (ppe_attack_*, statuses 25-28, ppe_format_attack_stat,
  * ppe_format_pkt_stat_atk), off until an object is attached; ppe_classify_host_ordered and
- * ppe_portscan_prepass_info */
+ * ppe_portscan_prepass_info; ppe_classify_flow_host and ppe_flow_launch_info */
 #define PPE_ABI_VERSION 8
 
 /* error codes (negative return values) */
@@ -413,11 +413,35 @@ typedef struct {
 int  ppe_flow_create(ppe_ctx_t *ctx, uint32_t capacity, uint32_t max_batch);
 int  ppe_flow_destroy(ppe_ctx_t *ctx);                                /* FlowRelease (flow.c:519-530) */
 /* FlowHandlePacket for a device-resident batch (same buffers as ppe_classify), stream-ordered on `stream`.
- * A batch is two launches (classify, then finalize + counter update).  If the second one cannot be launched, the call
+ * A batch is two launches (classify, then finalize + counter update); a small batch (at most PPE_FLOW_SMALL_CUTOFF
+ * packets, csrc/ppe_internal.h) is one launch of one workgroup that runs both phases, with the same results and the
+ * same table (PPE_FLOW_SMALL=0 in the environment at ppe_flow_create: always two; with monitors flow-attached: always
+ * two).  The two shapes interleave freely on one table.  If the second of two launches cannot be launched, the call
  * returns PPE_EIO and the table is unusable from then on: every later ppe_classify_flow / ppe_flow_age / _info /
  * _clear_stat / _dump returns PPE_EIO at once, until ppe_flow_destroy (or a new ppe_flow_create). */
 int  ppe_classify_flow(ppe_ctx_t *ctx, const ppe_batch_t *in, const ppe_result_t *out, const ppe_cfg_t *cfg,
                        void *stream);
+/* FlowHandlePacket for a host-resident batch (same buffers as ppe_classify_host).  Blocks until done.
+ * The per-packet outputs only: verdict (required), flow_hash, acl_hit, tuple.  A compacted list (fw_idx, drop_idx,
+ * tile_cnt, part8) or `packed` returns PPE_EINVAL before anything is touched (the post kernel has no index base for a
+ * chunk; lists across chunks are not built).
+ * The batch runs as consecutive ppe_classify_flow batches of `chunk` packets; H2D, both launches and D2H of every chunk
+ * go to one internal stream in chunk order (the stream of ppe_classify_host_ordered).  The flow path is exactly
+ * sequential and cfg->now_seconds is constant over the call, so the outputs, the counters and the whole table after
+ * the call are those of one core running the batch in index order, whatever `chunk` is: equal to one
+ * ppe_classify_flow of the same packets from device buffers.  `chunk` is rounded up to a multiple of 64 and clamped
+ * to the table's max_batch rounded down to one (max_batch below 64: PPE_EINVAL); 0 = min(1 << 18, that).
+ * When every buffer is pinned and device-mapped, n <= max_batch and PPE_HOST_ZEROCOPY is not 0, the kernels read and
+ * write the host buffers directly: one flow batch, no staging copy.
+ * PPE_ENOTSUP before touching anything: wherever ppe_classify_flow refuses (stream tracking on, a port-scan table
+ * attached, an object attached with ppe_attack_attach), and with an object attached with ppe_flow_attack_attach (its
+ * per-batch port array does not map onto chunks).  A broken table: PPE_EIO, as ppe_classify_flow.
+ * Flow batches submitted earlier on other streams must have completed (the internal stream does not wait for them). */
+int  ppe_classify_flow_host(ppe_ctx_t *ctx, const ppe_batch_t *in, const ppe_result_t *out, const ppe_cfg_t *cfg,
+                            uint32_t chunk);
+/* What the last flow batch of the context's table took: *kind 1 and *launches 1 (the one-launch kernel), or 0 and 2;
+ * 0 and 0 before the first batch.  NULL arguments: PPE_EINVAL. */
+int  ppe_flow_launch_info(ppe_ctx_t *ctx, uint32_t *kind, uint32_t *launches);
 /* FlowAgeTimeoutCB: delete flows with now > last_seen && now - last_seen > timeout_seconds; *deleted = count
  * (may be NULL).  Synchronises. */
 int  ppe_flow_age(ppe_ctx_t *ctx, uint64_t now_seconds, uint64_t timeout_seconds, uint64_t *deleted);

@@ -328,4 +328,11 @@ uint32_t ppe_pick_attack_flow(int flow, int flow_attached) {
     return (flow && flow_attached) ? 1u : 0u;
 }
 
+// one launch of one workgroup for a small flow batch (csrc/ppe_kernels_flow_small.hip): up to the measured cutoff,
+// unless the table was created without it or monitors are flow-attached (FLOW + ATK keeps the two launches: its
+// syncount_accum count lives in the post kernel)
+uint32_t ppe_pick_flow_small(uint32_t n, int small_allowed, int atk_flow_attached) {
+    return (n >= 1u && n <= PPE_FLOW_SMALL_CUTOFF && small_allowed && !atk_flow_attached) ? 1u : 0u;
+}
+
 }  // extern "C"

@@ -38,6 +38,12 @@ uint32_t portscan_able = 0;
 uint32_t portscan_action = 0;
 uint32_t portscan_exception_freq = 50;
 uint32_t flood_hold_time = 600;
+/* The flow table behind Decode (FlowHandlePacket, flow.c:181-310), read per classify call.  The reference has no such
+ * switch (every packet goes through its table); this library starts with it OFF, like the two above: set
+ * flow_able = 1 for the reference's behaviour.  flow_item_num: the pool (MEM_POOL_FLOW_NODE_NUM, mem_pool.h:72), read
+ * when the table is created. */
+uint32_t flow_able = 0;
+uint32_t flow_item_num = 100000;
 PluginModule plugin_modules[PLUGIN_SIZE];
 
 struct ppe_tree_set {
@@ -65,6 +71,10 @@ static pthread_mutex_t g_ctx_lock = PTHREAD_MUTEX_INITIALIZER;
  * clock DP_PortScan_Clock last gave; all under g_ctx_lock */
 static ppe_portscan_t *g_ps = NULL;
 static uint64_t g_ps_cycles = 0, g_ps_seconds = 0;
+/* the context has the shim's flow table (created by the first flush with flow_able == 1, destroyed with the context)
+ * and the clock DP_Flow_Clock last gave; both under g_ctx_lock */
+static int g_flow = 0;
+static uint64_t g_flow_now = 0;
 static fw_alert fw_log_fun = NULL;
 static ppe_output_fn out_fw = NULL, out_drop = NULL, out_punt = NULL;
 
@@ -177,8 +187,9 @@ void DP_Acl_Rule_Release(void) {
     pthread_mutex_lock(&g_ctx_lock);  /* no flush, commit or lookup is using the context being destroyed */
     if (g_ps) ppe_portscan_destroy(g_ps);  /* (before its context) */
     g_ps = NULL;
-    if (g_ctx) ppe_ctx_destroy(g_ctx);
+    if (g_ctx) ppe_ctx_destroy(g_ctx);  /* (its flow table with it) */
     g_ctx = NULL;
+    g_flow = 0;
     g_published = 0;  /* (a new context numbers its tokens from 1 again) */
     pthread_mutex_unlock(&g_ctx_lock);
     write_lock(&acltree_running_rwlock);
@@ -351,9 +362,10 @@ static int logged_drop(uint32_t st) {
  * outputs for the packet (verdict, tuple) and its length.  Which layer wrote what follows from the terminal status:
  * the decoders run in order and each writes its fields once its own checks have passed.  Header pointers are the
  * packet's own addresses at the offsets the decoders use (IPV4_GET_HLEN / TCP_GET_HLEN read the same header bytes
- * the reference reads); no field is derived by re-decoding the packet here.  The stateless path has no flow object:
- * m->flow stays as it was (FlowHandlePacket sets it to the flow item, flow.c:306). */
-static void fill_mbuf(mbuf_t *m, uint32_t v, uint32_t fhash, int32_t hit, const uint32_t *tu) {
+ * the reference reads); no field is derived by re-decoding the packet here.  There is no host flow object, with or
+ * without the flow table: m->flow stays as it was (FlowHandlePacket sets it to the flow item, flow.c:306).
+ * flow_on: the burst went through the flow table (flow_able == 1). */
+static void fill_mbuf(mbuf_t *m, uint32_t v, uint32_t fhash, int32_t hit, const uint32_t *tu, int flow_on) {
     const uint32_t st = PPE_VERDICT_STATUS(v), fl = PPE_VERDICT_FLAGS(v);
     uint8_t *pkt = (uint8_t *)m->pkt_ptr;
     m->ppe_verdict = v;
@@ -413,8 +425,37 @@ static void fill_mbuf(mbuf_t *m, uint32_t v, uint32_t fhash, int32_t hit, const 
      * is its flow's first, and FlowAdd orients the flow as that packet, so the direction is to-server.
      * StreamTcp runs after that (flow.c:311-320), so a packet it drops carries the flags too.  A packet the port-scan
      * detector dropped has no flow: FlowGetFlowFromHash returned NULL before FlowAdd (flow.c:216-230). */
+    if (flow_on) {
+        /* the flow table: the kernel's own flags (flow.c:248-307): a found or created flow, its direction against the
+         * packet that created it; a FLOW_NOMEM, NO_SYN_FIRST or ACL-dropped packet has no flow and carries neither */
+        if (fl & PPE_F_FLOW) m->flags |= PKT_HAS_FLOW | ((fl & PPE_F_TOCLIENT) ? PKT_TO_CLIENT : PKT_TO_SERVER);
+        return;
+    }
     if (st == PPE_ST_ACL_FW || (st >= PPE_ST_STREAM_RST_NO_SESSION && st <= PPE_ST_STREAM_MIDSTREAM_OFF))
         m->flags |= PKT_TO_SERVER | PKT_HAS_FLOW;
+}
+
+/* FlowInit behind Decode, caller holds g_ctx_lock and g_ctx is set: the table on first use (flow_item_num flows;
+ * max_batch at least this burst: a later, larger burst goes through it in chunks). */
+static int flow_prepare_locked(uint32_t n) {
+    if (g_flow) return PPE_OK;
+    const int rc = ppe_flow_create(g_ctx, flow_item_num, ((n > 4096u ? n : 4096u) + 63u) & ~63u);
+    if (rc == PPE_OK) g_flow = 1;
+    return rc;
+}
+
+void DP_Flow_Clock(uint64_t now_seconds) {
+    pthread_mutex_lock(&g_ctx_lock);
+    g_flow_now = now_seconds;
+    pthread_mutex_unlock(&g_ctx_lock);
+}
+
+int DP_Flow_Age(uint64_t now_seconds, uint64_t *deleted) {
+    if (deleted) *deleted = 0;
+    pthread_mutex_lock(&g_ctx_lock);
+    const int rc = (g_ctx && g_flow) ? ppe_flow_age(g_ctx, now_seconds, 20u /* FLOW_MAX_TIMEOUT */, deleted) : PPE_OK;
+    pthread_mutex_unlock(&g_ctx_lock);
+    return rc;
 }
 
 /* PortScan_Detect behind Decode (flow.c:215-230), caller holds g_ctx_lock and g_ctx is set: the table on first use
@@ -486,19 +527,32 @@ static int classify_mbufs(mbuf_t **mb, uint32_t n) {
         ppe_cfg_t cfg = {unsupport_proto_action ? 1u : 0u, syn_check ? 1u : 0u, 0};
         const ppe_stream_tcp_cfg_t stcp = {stream_tcp_track_enable ? 1u : 0u, stream_tcp_midstream ? 1u : 0u,
                                            stream_tcp_async_oneside ? 1u : 0u, 0u};
+        const int flow_on = flow_able == 1u;  /* (any other value is off) */
         pthread_mutex_lock(&g_ctx_lock);
         sync_running_locked();
-        rc = g_ctx ? ppe_stream_tcp_set(g_ctx, &stcp) : PPE_ENODEV;
+        if (flow_on) cfg.now_seconds = g_flow_now;  /* FLOW_UPDATE_TIMESTAMP's clock */
+        if (g_ctx && flow_on && (portscan_able == 1u || stream_tcp_track_enable)) {
+            /* the detector on flow misses only and the TCP session machine are not built: the burst is refused before
+             * any state changes (ppe_decode.h) */
+            rc = PPE_ENOTSUP;
+        } else {
+            rc = g_ctx ? ppe_stream_tcp_set(g_ctx, &stcp) : PPE_ENODEV;
+        }
         if (rc == PPE_OK && portscan_able == 1u) {  /* (dp_portscan.c:238: any other value is off) */
             rc = portscan_prepare_locked(n);
             if (rc == PPE_OK) rc = ppe_classify_host_ordered(g_ctx, &b, &r, &cfg, 0);
         } else if (rc == PPE_OK) {
             if (g_ps) rc = ppe_portscan_attach(g_ctx, NULL);  /* the table keeps its records while off */
-            if (rc == PPE_OK) rc = ppe_classify_host(g_ctx, &b, &r, &cfg, 0);
+            if (rc == PPE_OK && flow_on) {  /* FlowHandlePacket: the table on first use, the burst in order through it */
+                rc = flow_prepare_locked(n);
+                if (rc == PPE_OK) rc = ppe_classify_flow_host(g_ctx, &b, &r, &cfg, 0);
+            } else if (rc == PPE_OK) {
+                rc = ppe_classify_host(g_ctx, &b, &r, &cfg, 0);
+            }
         }
         pthread_mutex_unlock(&g_ctx_lock);
         if (rc == PPE_OK)
-            for (uint32_t i = 0; i < n; i++) fill_mbuf(mb[i], verdict[i], fh[i], hit[i], tuple + 4 * (size_t)i);
+            for (uint32_t i = 0; i < n; i++) fill_mbuf(mb[i], verdict[i], fh[i], hit[i], tuple + 4 * (size_t)i, flow_on);
     }
     free(hdr);
     free(len);

@@ -96,6 +96,10 @@ struct FlowTable {
     // finalized (miss-tile counter, snapshot, creators), so every later call on the table fails until
     // ppe_flow_destroy / ppe_flow_create
     bool broken = false;
+    // batches of at most PPE_FLOW_SMALL_CUTOFF packets take the one-launch kernel (PPE_FLOW_SMALL=0 at ppe_flow_create:
+    // never, the A/B switch); what the last batch took, for ppe_flow_launch_info
+    bool small_allowed = true;
+    uint32_t last_kind = 0, last_launches = 0;
 };
 
 }  // namespace
@@ -654,9 +658,11 @@ int ps_prepass(ppe_ctx *c, const ppe_batch_t *in, uint32_t nb, const ppe_cfg_t *
 
 // One launch over batches in[0..nb) (nb <= PPE_MAX_RING, each n > 0): every wave takes its tiles of batch 0, then
 // of batch 1, ... (no barrier between batches, one image staging for all of them).
+// small (flow-table launches only): the one-launch kernel of one 1024-thread workgroup, classify then finalize, with
+// finalize's own arguments
 int launch(ppe_ctx *c, const ppe_batch_t *in, const ppe_result_t *out, uint32_t nb, const ppe_cfg_t *cfg,
            hipStream_t s, int slot_set, uint32_t idx_base = 0, const ppe_flowdev *fl = nullptr,
-           uint32_t *grid_out = nullptr, uint32_t atk_pbase = 0) {
+           uint32_t *grid_out = nullptr, uint32_t atk_pbase = 0, const ppe_flow_small_tail *small = nullptr) {
     const int r = c->running;
     const ppe_plan &plan = c->plan[r][fl != nullptr];
     ppe_kargs a;
@@ -721,7 +727,7 @@ int launch(ppe_ctx *c, const ppe_batch_t *in, const ppe_result_t *out, uint32_t 
     const uint32_t wpb = plan.block / 64u;
     const uint32_t want = (uint32_t)std::min<uint64_t>((sh.tiles_total + wpb - 1) / wpb, 1u << 30);
     const uint32_t maxg = c->n_cu * blocks_per_cu(c, r, fl != nullptr);
-    const uint32_t grid = std::max(1u, std::min(want, std::min(maxg, c->max_grid)));
+    const uint32_t grid = small ? 1u : std::max(1u, std::min(want, std::min(maxg, c->max_grid)));
     if (grid_out) *grid_out = grid;
 
     // the timing events are taken before the launch takes its completion slot: nothing between track_launch and the
@@ -740,8 +746,9 @@ int launch(ppe_ctx *c, const ppe_batch_t *in, const ppe_result_t *out, uint32_t 
     }
     rc = track_launch(c, grid, a);
     if (rc != PPE_OK) return rc;
-    rc = ppe_launch_classify(&a, grid, (int)plan.mode, (int)plan.pipe, (int)plan.block, fl != nullptr, (void *)s,
-                             (void *)e0, (void *)e1);
+    rc = small ? ppe_launch_flow_small(&a, small, (int)plan.mode, (void *)s, (void *)e0, (void *)e1)
+               : ppe_launch_classify(&a, grid, (int)plan.mode, (int)plan.pipe, (int)plan.block, fl != nullptr, (void *)s,
+                                     (void *)e0, (void *)e1);
     if (rc != 0) {
         untrack_launch(c, grid, a);
         return fail(c, PPE_EIO, "kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
@@ -1066,6 +1073,31 @@ static const void *mapped_host(const void *p) {
     return (const char *)at.devicePointer + ((const char *)p - (const char *)at.hostPointer);
 }
 
+// the staging slots of the host-buffer calls: a stream each, and device buffers for `chunk` packets of `stride` bytes
+static int host_stages_reserve(ppe_ctx_t *c, uint32_t chunk, uint32_t stride) {
+    for (auto &h : c->hs) {
+        if (!h.s) HIPCHK(c, hipStreamCreateWithFlags(&h.s, hipStreamNonBlocking));
+        if (h.cap < chunk || h.stride != stride) {
+            (void)hipFree(h.hdr); (void)hipFree(h.len); (void)hipFree(h.ts); (void)hipFree(h.verdict); (void)hipFree(h.fhash);
+            (void)hipFree(h.hit); (void)hipFree(h.fw); (void)hipFree(h.drop); (void)hipFree(h.tcnt); (void)hipFree(h.tuple);
+            h = HostStage{h.s};
+            HIPCHK(c, hipMalloc(&h.hdr, (size_t)chunk * stride));
+            HIPCHK(c, hipMalloc(&h.len, (size_t)chunk * 4));
+            HIPCHK(c, hipMalloc(&h.ts, (size_t)chunk * 8));
+            HIPCHK(c, hipMalloc(&h.verdict, (size_t)chunk * 4));
+            HIPCHK(c, hipMalloc(&h.fhash, (size_t)chunk * 4));
+            HIPCHK(c, hipMalloc(&h.hit, (size_t)chunk * 4));
+            HIPCHK(c, hipMalloc(&h.fw, (size_t)chunk * 4));
+            HIPCHK(c, hipMalloc(&h.drop, (size_t)chunk * 4));
+            HIPCHK(c, hipMalloc(&h.tcnt, (size_t)(chunk / 64) * 4));
+            HIPCHK(c, hipMalloc(&h.tuple, (size_t)chunk * 16));
+            h.cap = chunk;
+            h.stride = stride;
+        }
+    }
+    return PPE_OK;
+}
+
 // ppe_classify_host (ordered false: the chunks' launches on the staging slots' streams) and
 // ppe_classify_host_ordered with the detector on (ordered: every chunk's pre-pass and classify launch on c->host_cs, in
 // chunk order; the copies go to host_cs too, or stay on the slots' streams with an event each way)
@@ -1108,26 +1140,8 @@ static int classify_host_run(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_resu
                 for (hipEvent_t &e : pair)
                     if (!e) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
-    for (auto &h : c->hs) {
-        if (!h.s) HIPCHK(c, hipStreamCreateWithFlags(&h.s, hipStreamNonBlocking));
-        if (h.cap < chunk || h.stride != in->stride) {
-            (void)hipFree(h.hdr); (void)hipFree(h.len); (void)hipFree(h.ts); (void)hipFree(h.verdict); (void)hipFree(h.fhash);
-            (void)hipFree(h.hit); (void)hipFree(h.fw); (void)hipFree(h.drop); (void)hipFree(h.tcnt); (void)hipFree(h.tuple);
-            h = HostStage{h.s};
-            HIPCHK(c, hipMalloc(&h.hdr, (size_t)chunk * in->stride));
-            HIPCHK(c, hipMalloc(&h.len, (size_t)chunk * 4));
-            HIPCHK(c, hipMalloc(&h.ts, (size_t)chunk * 8));
-            HIPCHK(c, hipMalloc(&h.verdict, (size_t)chunk * 4));
-            HIPCHK(c, hipMalloc(&h.fhash, (size_t)chunk * 4));
-            HIPCHK(c, hipMalloc(&h.hit, (size_t)chunk * 4));
-            HIPCHK(c, hipMalloc(&h.fw, (size_t)chunk * 4));
-            HIPCHK(c, hipMalloc(&h.drop, (size_t)chunk * 4));
-            HIPCHK(c, hipMalloc(&h.tcnt, (size_t)(chunk / 64) * 4));
-            HIPCHK(c, hipMalloc(&h.tuple, (size_t)chunk * 16));
-            h.cap = chunk;
-            h.stride = in->stride;
-        }
-    }
+    rc = host_stages_reserve(c, chunk, in->stride);
+    if (rc != PPE_OK) return rc;
     const hipMemcpyKind h2d = hipMemcpyHostToDevice, d2h = hipMemcpyDeviceToHost;
     for (uint32_t base = 0, i = 0; base < in->n; base += chunk, ++i) {
         HostStage &h = c->hs[i % kHostStreams];
@@ -2012,6 +2026,7 @@ int ppe_flow_create(ppe_ctx_t *c, uint32_t capacity, uint32_t max_batch) {
     t->capacity = capacity;
     t->max_batch = max_batch;
     t->use_event = env_int("PPE_FLOW_EVENT", 0) != 0;
+    t->small_allowed = env_int("PPE_FLOW_SMALL", 1) != 0;
     // finalize on half the CUs: the update workgroups (one per CU by their LDS) start on the other half at once
     // (F1 batch 67.1 -> 66.3 µs against one per CU, 69.3 / 71.9 at 64 / 32: profiles/r5_ab_runs.md r5aq)
     t->fin_cap = (uint32_t)std::max(0, env_int("PPE_FLOW_FIN_WGS", (int)std::max(1u, c->n_cu / 2u)));
@@ -2103,50 +2118,67 @@ int ppe_classify_flow(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *o
     const hipStream_t s = (hipStream_t)stream;
     const ppe_flowdev d = flow_dev(t, t.cur);
     if (t.use_event) HIPCHK(c, hipEventRecord(t.pre_launch, s));
-    // 1. decode, hash, FlowFind; found flows are forwarded and their updates logged to the owners' buckets, the
-    // rest get syn_check + ACL (would-be creators claim their slots)
-    uint32_t cgrid = 0;
-    rc = launch(c, in, out, 1, cfg, s, 0, 0, &d, &cgrid);
-    if (rc != PPE_OK) return rc;
-    ppe_flow_kargs k;
-    std::memset(&k, 0, sizeof k);
-    k.f = d;
-    k.f.upd_grid = cgrid;
-    k.len = in->len;
-    k.verdict = out->verdict;
-    k.hit = out->acl_hit;
-    k.fw_idx = out->fw_idx;
-    k.drop_idx = out->drop_idx;
-    k.tile_cnt = out->tile_cnt;
-    k.part8 = out->part8;
-    k.n = in->n;
-    k.unsup_fw = cfg ? cfg->unsupport_proto_action : 0u;
-    k.now = cfg ? cfg->now_seconds : 0u;
-    k.nslots = t.nslots;
-    k.cslots = c->d_cslots;
-    if (ppe_pick_attack_flow(1, c->atk_flow != nullptr)) {  // syncount_accum: the flows this batch's SYNs create
-        k.atk_slots = c->atk_flow->d_slots;
-        k.atk_pb = c->atk_flow->h_ports.empty() ? nullptr : c->atk_flow->h_ports[0];
-    }
-    // 2. the post-classify launch: finalize (grid-stride over the miss-tile list, usually short: at most one
-    // workgroup per CU) and, beside it, the found flows' counters and last-seen times, one workgroup per owner
-    // (disjoint from the slots finalize touches).  When the host's bound says the pool may overflow, finalize checks
-    // the exact counts and, on an overflow, marks the creators and has its workgroup 0 revoke those past the pool's
-    // room first.
-    // (fg <= n_cu <= max_grid: the finalize workgroups' indices stay inside the monitors' max_grid count slots)
-    const uint32_t fg = std::min(std::min(flow_grid(c, (in->n + 63u) / 64u, PPE_FLOW_POST_BLOCK / 64u), c->n_cu),
-                                 t.fin_cap ? t.fin_cap : c->n_cu);
+    // (the same for both launch shapes: the host's bounds, the snapshot ring and the parity follow the batch)
     const bool may_overflow = t.live_ub + in->n > t.capacity;
-    k.revoke = may_overflow ? 1u : 0u;
-    k.fin_wgs = fg;
-    {
-        const int e = take_fail_post() ? (int)hipErrorLaunchFailure
-                                       : ppe_launch_flow(PPE_FLOW_K_POST, &k, fg + (t.upd_wgs ? t.upd_owners : 0u), (void *)s);
-        if (e != 0) {
-            t.broken = true;  // the classify launch above claimed slots that nothing will finalize
-            return fail(c, PPE_EIO, "flow post-classify launch failed: %s", hipGetErrorString((hipError_t)e));
+    // a small batch: classify and finalize in one launch of one workgroup, the found flows' updates by the direct
+    // atomics (no owner buckets, no update workgroups).  Not with monitors flow-attached (their syncount count lives
+    // in the post kernel), not while the post-launch failure hook is armed
+    const bool small = ppe_pick_flow_small(in->n, t.small_allowed && __atomic_load_n(&g_fail_post, __ATOMIC_RELAXED) == 0u,
+                                           c->atk_flow != nullptr) != 0u;
+    if (small) {
+        ppe_flowdev ds = d;
+        ds.upd_wgs = 0;
+        const ppe_flow_small_tail tail = {in->len,      out->verdict, out->acl_hit, out->fw_idx, out->drop_idx,
+                                          out->tile_cnt, out->part8,  may_overflow ? 1u : 0u, 0u};
+        rc = launch(c, in, out, 1, cfg, s, 0, 0, &ds, nullptr, 0, &tail);
+        if (rc != PPE_OK) return rc;  // (nothing ran: the table is as it was)
+    } else {
+        // 1. decode, hash, FlowFind; found flows are forwarded and their updates logged to the owners' buckets, the
+        // rest get syn_check + ACL (would-be creators claim their slots)
+        uint32_t cgrid = 0;
+        rc = launch(c, in, out, 1, cfg, s, 0, 0, &d, &cgrid);
+        if (rc != PPE_OK) return rc;
+        ppe_flow_kargs k;
+        std::memset(&k, 0, sizeof k);
+        k.f = d;
+        k.f.upd_grid = cgrid;
+        k.len = in->len;
+        k.verdict = out->verdict;
+        k.hit = out->acl_hit;
+        k.fw_idx = out->fw_idx;
+        k.drop_idx = out->drop_idx;
+        k.tile_cnt = out->tile_cnt;
+        k.part8 = out->part8;
+        k.n = in->n;
+        k.unsup_fw = cfg ? cfg->unsupport_proto_action : 0u;
+        k.now = cfg ? cfg->now_seconds : 0u;
+        k.nslots = t.nslots;
+        k.cslots = c->d_cslots;
+        if (ppe_pick_attack_flow(1, c->atk_flow != nullptr)) {  // syncount_accum: the flows this batch's SYNs create
+            k.atk_slots = c->atk_flow->d_slots;
+            k.atk_pb = c->atk_flow->h_ports.empty() ? nullptr : c->atk_flow->h_ports[0];
+        }
+        // 2. the post-classify launch: finalize (grid-stride over the miss-tile list, usually short: at most one
+        // workgroup per CU) and, beside it, the found flows' counters and last-seen times, one workgroup per owner
+        // (disjoint from the slots finalize touches).  When the host's bound says the pool may overflow, finalize checks
+        // the exact counts and, on an overflow, marks the creators and has its workgroup 0 revoke those past the pool's
+        // room first.
+        // (fg <= n_cu <= max_grid: the finalize workgroups' indices stay inside the monitors' max_grid count slots)
+        const uint32_t fg = std::min(std::min(flow_grid(c, (in->n + 63u) / 64u, PPE_FLOW_POST_BLOCK / 64u), c->n_cu),
+                                     t.fin_cap ? t.fin_cap : c->n_cu);
+        k.revoke = may_overflow ? 1u : 0u;
+        k.fin_wgs = fg;
+        {
+            const int e = take_fail_post() ? (int)hipErrorLaunchFailure
+                                           : ppe_launch_flow(PPE_FLOW_K_POST, &k, fg + (t.upd_wgs ? t.upd_owners : 0u), (void *)s);
+            if (e != 0) {
+                t.broken = true;  // the classify launch above claimed slots that nothing will finalize
+                return fail(c, PPE_EIO, "flow post-classify launch failed: %s", hipGetErrorString((hipError_t)e));
+            }
         }
     }
+    t.last_kind = small ? 1u : 0u;
+    t.last_launches = small ? 1u : 2u;
     t.cum_n[t.batches % FlowTable::kSnapRing] = t.tot_n;
     t.cum_rev[t.batches % FlowTable::kSnapRing] = t.tot_rev;
     t.tot_n += in->n;
@@ -2154,6 +2186,90 @@ int ppe_classify_flow(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *o
     ++t.batches;
     t.live_ub = std::min<uint64_t>(t.live_ub + in->n, t.capacity);
     if (may_overflow) t.tomb_ub += in->n;  // revoked claims leave tombstones
+    return PPE_OK;
+}
+
+// ppe_classify_flow for a host-resident batch: consecutive flow batches of at most `chunk` packets, every copy and
+// launch on c->host_cs in chunk order.  The flow path is exactly sequential, so the chunk size changes nothing.
+int ppe_classify_flow_host(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *out, const ppe_cfg_t *cfg,
+                           uint32_t chunk) {
+    if (!c || !out) return PPE_EINVAL;
+    if (const int u = flow_usable(c)) return u;
+    if (!out->verdict) return fail(c, PPE_EINVAL, "ppe_classify_flow_host needs the verdict output");
+    // the post kernel has no index base for a chunk's lists
+    if (out->fw_idx || out->drop_idx || out->tile_cnt || out->part8 || out->packed)
+        return fail(c, PPE_EINVAL, "ppe_classify_flow_host takes the per-packet outputs only (no lists, no packed)");
+    // ppe_classify_flow's refusals, before anything is touched
+    if (c->stcp.track) return fail(c, PPE_ENOTSUP, "ppe_classify_flow_host with stream tracking on is not supported");
+    if (c->ps) return fail(c, PPE_ENOTSUP, "ppe_classify_flow_host with a port-scan table attached is not supported");
+    if (c->atk) return fail(c, PPE_ENOTSUP, "ppe_classify_flow_host with attack monitors attached is not supported");
+    // the monitors' per-batch port array does not map onto chunks (as ppe_classify_host_ordered)
+    if (c->atk_flow)
+        return fail(c, PPE_ENOTSUP, "ppe_classify_flow_host with attack monitors flow-attached is not supported");
+    int rc = check_batch(c, in, cfg);
+    if (rc != PPE_OK || in->n == 0) return rc;
+    const uint32_t cmax = c->flow->max_batch & ~63u;
+    if (cmax < 64u) return fail(c, PPE_EINVAL, "ppe_classify_flow_host: the flow table's max_batch is below one tile");
+    HIPCHK(c, use_device(c));
+    if (!c->host_cs) HIPCHK(c, hipStreamCreateWithFlags(&c->host_cs, hipStreamNonBlocking));
+    const hipStream_t s = c->host_cs;
+    // Zero-copy: every buffer pinned and device-mapped, one batch: the kernels read and write the host buffers
+    if (env_int("PPE_HOST_ZEROCOPY", 1) && in->n <= c->flow->max_batch) {
+        ppe_batch_t b = *in;
+        ppe_result_t r = *out;
+        bool ok = (b.hdr = (const uint8_t *)mapped_host(in->hdr)) && (b.len = (const uint32_t *)mapped_host(in->len));
+        if (in->ts) ok = ok && (b.ts = (const uint64_t *)mapped_host(in->ts));
+        uint32_t **outs[] = {&r.verdict, &r.flow_hash, (uint32_t **)&r.acl_hit, &r.tuple};
+        for (uint32_t **o : outs)
+            if (ok && *o) ok = (*o = (uint32_t *)mapped_host(*o)) != nullptr;
+        if (ok) {
+            rc = ppe_classify_flow(c, &b, &r, cfg, (void *)s);
+            HIPCHK(c, hipStreamSynchronize(s));
+            return rc;
+        }
+    }
+    if (chunk == 0) chunk = 1u << 18;
+    chunk = (chunk + 63u) & ~63u;
+    chunk = std::min(std::min(chunk, cmax), (in->n + 63u) & ~63u);
+    rc = host_stages_reserve(c, chunk, in->stride);
+    if (rc != PPE_OK) return rc;
+    const hipMemcpyKind h2d = hipMemcpyHostToDevice, d2h = hipMemcpyDeviceToHost;
+    hipError_t he = hipSuccess;
+    for (uint32_t base = 0, i = 0; base < in->n && rc == PPE_OK && he == hipSuccess; base += chunk, ++i) {
+        HostStage &h = c->hs[i % kHostStreams];  // (one stream: a slot's reuse follows its last download)
+        const uint32_t m = std::min(chunk, in->n - base);
+        he = hipMemcpyAsync(h.hdr, in->hdr + (size_t)base * in->stride, (size_t)m * in->stride, h2d, s);
+        if (he == hipSuccess) he = hipMemcpyAsync(h.len, in->len + base, (size_t)m * 4, h2d, s);
+        if (he == hipSuccess && in->ts) he = hipMemcpyAsync(h.ts, in->ts + base, (size_t)m * 8, h2d, s);
+        if (he != hipSuccess) break;
+        ppe_batch_t b = {h.hdr, h.len, in->ts ? h.ts : nullptr, m, in->stride};
+        ppe_result_t r;
+        std::memset(&r, 0, sizeof r);
+        r.verdict = h.verdict;
+        r.flow_hash = out->flow_hash ? h.fhash : nullptr;
+        r.acl_hit = out->acl_hit ? h.hit : nullptr;
+        r.tuple = out->tuple ? h.tuple : nullptr;
+        rc = ppe_classify_flow(c, &b, &r, cfg, (void *)s);
+        if (rc != PPE_OK) break;
+        he = hipMemcpyAsync(out->verdict + base, h.verdict, (size_t)m * 4, d2h, s);
+        if (he == hipSuccess && out->flow_hash) he = hipMemcpyAsync(out->flow_hash + base, h.fhash, (size_t)m * 4, d2h, s);
+        if (he == hipSuccess && out->acl_hit) he = hipMemcpyAsync(out->acl_hit + base, h.hit, (size_t)m * 4, d2h, s);
+        if (he == hipSuccess && out->tuple)
+            he = hipMemcpyAsync(out->tuple + (size_t)base * 4, h.tuple, (size_t)m * 16, d2h, s);
+    }
+    // (also after a failure: no copy into the caller's buffers is left in flight)
+    const hipError_t se = hipStreamSynchronize(s);
+    if (rc != PPE_OK) return rc;
+    HIPCHK(c, he);
+    HIPCHK(c, se);
+    return PPE_OK;
+}
+
+int ppe_flow_launch_info(ppe_ctx_t *c, uint32_t *kind, uint32_t *launches) {
+    if (!c || !kind || !launches) return PPE_EINVAL;
+    if (const int u = flow_usable(c)) return u;
+    *kind = c->flow->last_kind;
+    *launches = c->flow->last_launches;
     return PPE_OK;
 }
 

@@ -131,6 +131,24 @@ struct ppe_flow_kargs {
     };
 };
 
+/* ---- one launch for small flow batches (csrc/ppe_kernels_flow_small.hip) ----
+ * A flow batch of 1 <= n <= PPE_FLOW_SMALL_CUTOFF packets runs classify and finalize in one launch of one 1024-thread
+ * workgroup instead of two launches sized for 1M-packet batches (ppe_pick_flow_small).  A multiple of 64, at least 64,
+ * at most 2,048, and never above the largest size at which tools/ab_flow_small.py's measurement supports it. */
+#define PPE_FLOW_SMALL_CUTOFF 512u
+#define PPE_FLOW_SMALL_BLOCK 1024
+/* what finalize needs beside the classify arguments (ppe_flow_kargs' fields of the same names; n, unsup_fw, now, the
+ * counter slots and the table come from ppe_kargs) */
+struct ppe_flow_small_tail {
+    const uint32_t *len;
+    uint32_t *verdict;
+    int32_t *hit;
+    uint32_t *fw_idx, *drop_idx, *tile_cnt;
+    uint8_t *part8;
+    uint32_t revoke;
+    uint32_t pad;
+};
+
 /* batches per launch whose descriptors travel in the kernel arguments (32 × 96 B); a launch over more batches reads
  * them from a device descriptor ring (ppe_kargs.ring) */
 #define PPE_MAX_BATCH 32
@@ -224,6 +242,13 @@ struct ppe_kargs {
             uint32_t atk_pbase;                  /* the call's batch index of this launch's batch 0 */
         };
     };
+};
+
+/* the one-launch flow kernel's own argument block: the classify arguments (ppe_kargs keeps its size and offsets), then
+ * finalize's */
+struct ppe_flow_small_kargs {
+    struct ppe_kargs k;
+    struct ppe_flow_small_tail t;
 };
 
 /* ---- attack monitors (csrc/ppe_attack.hip, the ATK classify kernels; dataplane/src/attack/dp_attack.c) ----
@@ -426,6 +451,10 @@ uint32_t ppe_pick_attack(int flow, int attached);
  * syncount_accum per created flow: a flow-table launch of a context with an object flow-attached
  * (ppe_flow_attack_attach), and no other launch */
 uint32_t ppe_pick_attack_flow(int flow, int flow_attached);
+/* 1: the flow batch of n packets takes the one-launch kernel: 1 <= n <= PPE_FLOW_SMALL_CUTOFF, the table allows it
+ * (small_allowed: not created under PPE_FLOW_SMALL=0, the post-launch failure hook not armed) and no monitors are
+ * flow-attached (their syncount count lives in the post kernel); else 0, the two launches */
+uint32_t ppe_pick_flow_small(uint32_t n, int small_allowed, int atk_flow_attached);
 /* the monitors' set / tick / clear kernel (csrc/ppe_attack.hip), stream-ordered.  Returns hipError_t */
 int ppe_launch_attack_ctl(const struct ppe_atk_kargs *a, void *stream);
 /* one kernel of the port-scan pre-pass (csrc/ppe_portscan.hip), grid sized from the arguments.  Returns hipError_t */
@@ -438,6 +467,10 @@ int ppe_launch_classify(const struct ppe_kargs *a, uint32_t grid, int mode, int 
  * workgroup 0 when the pool overflows) */
 enum { PPE_FLOW_K_POST = 0, PPE_FLOW_K_AGE, PPE_FLOW_K_REHASH };
 int ppe_launch_flow(int kind, const struct ppe_flow_kargs *a, uint32_t grid, void *stream);
+/* the one-launch flow kernel over the image placement `mode` (csrc/ppe_kernels_flow_small.hip): one workgroup of
+ * PPE_FLOW_SMALL_BLOCK threads; a->flow.upd_wgs must be 0.  Returns hipError_t */
+int ppe_launch_flow_small(const struct ppe_kargs *a, const struct ppe_flow_small_tail *t, int mode, void *stream,
+                          void *ev_start, void *ev_stop);
 #define PPE_FLOW_BLOCK 256      /* flow kernels' workgroup size */
 /* steering: 0 count, 1 scan (one workgroup), 2 scatter the permutation; rows: gather / scatter of fixed rows */
 int ppe_launch_steer(int phase, const struct ppe_steer_kargs *a, uint32_t grid, void *stream);

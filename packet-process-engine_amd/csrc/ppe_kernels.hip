@@ -1415,14 +1415,21 @@ __device__ __forceinline__ void atk_count(uint32_t *bins, uint32_t flags) {
 // the decoders, ahead of FlowFind, so a packet they drop leaves decode() as a decode error does (no PPE_F_L4): no
 // lookup, no claim, no record, not a miss.  syncount_accum is not counted here: it counts the flows SYNs create,
 // which the post launch knows (flow_finalize_wg).
+// (csrc/ppe_kernels_flow_small.hip builds this body as a function, classify_body, the first phase of its one-launch
+// kernel, and has no ppe_classify_kernel: giving the body a function form that this kernel calls moved instructions in
+// it, DESIGN.md §5.10, so only the header differs and every other unit compiles the text it always did)
 template <int MODE, int PF, int BLOCK, bool FLOW, bool PART = false, bool STM = false, bool PSC = false,
           bool ATK = false>
+#if defined(PPE_TU_FLOW_SMALL)
+__device__ __forceinline__ void classify_body(const ppe_kargs &a) {
+#else
 __global__ __launch_bounds__(BLOCK, (PF == PF_MULTI && !FLOW) ? PPE_MT_WAVES
                                     : FLOW                                       ? PPE_FLOW_WAVES
                                     : (PF == PF_CUT && MODE == IMG_LDS)          ? PPE_CUT_LDS_WAVES
                                     : (PF == PF_CUT && MODE == IMG_SPLIT)        ? PPE_CUT_SPLIT_WAVES
                                                                                  : PPE_WAVES_PER_EU)
 void ppe_classify_kernel(ppe_kargs a) {
+#endif
     // the multi-tile kernel over a whole-LDS image runs the software-pipelined round loop: the next round's windows
     // are requested before the walk (vmcnt retires loads in issue order; the walk and the record check there issue
     // no global loads, so nothing waits for the prefetch early).  Split images keep the plain round loop: their
@@ -2072,7 +2079,14 @@ __device__ __forceinline__ void flow_revoke(const ppe_flow_kargs &a, uint32_t *p
 // that creates its flow adds 1 to its input port's syncount_accum (DP_Attack_SynCountMonitor sits in FlowAdd behind
 // flow_item_alloc, flow.c:151-154: not a packet that finds the flow, not a revoked creator).  Counted per port and
 // tile by ballot, summed per workgroup in LDS, one add per non-empty port into the workgroup's own count slot
+// (csrc/ppe_kernels_flow_small.hip: the same body over LDS its kernel provides, a part of the dynamic LDS whose layout
+// the classify phase fixes; nothing static may sit in front of that)
 template <int BLOCK, bool ATK = false>
+#if defined(PPE_TU_FLOW_SMALL)
+__device__ __forceinline__ void flow_finalize_wg(const ppe_flow_kargs &a, uint32_t nwg, uint32_t *bins, uint32_t *lcnt,
+                                                 uint32_t *part, uint32_t &rev_s, unsigned long long &room_s,
+                                                 uint32_t *syn_new) {
+#else
 __device__ __forceinline__ void flow_finalize_wg(const ppe_flow_kargs &a, uint32_t nwg) {
     __shared__ uint32_t bins[PPE_NBINS];
     __shared__ uint32_t lcnt[32];
@@ -2080,6 +2094,7 @@ __device__ __forceinline__ void flow_finalize_wg(const ppe_flow_kargs &a, uint32
     __shared__ uint32_t rev_s;
     __shared__ unsigned long long room_s;
     __shared__ uint32_t syn_new[ATK ? 4 : 1];  // ATK: this workgroup's SYN-created flows per port
+#endif
     const uint32_t tid = threadIdx.x;
     for (uint32_t i = tid; i < PPE_NBINS; i += BLOCK) bins[i] = 0;
     if (tid < 32u) lcnt[tid] = 0;
@@ -2406,6 +2421,7 @@ __device__ __forceinline__ void flow_update_wg(const ppe_flow_kargs &a, uint32_t
 // The launch after a flow-mode classify launch: finalize on workgroups [0, fin_wgs) and the owner-computed update on
 // the next upd_owners workgroups, side by side (they touch disjoint slots: finalize the ones claimed in this batch,
 // the update the found flows'), so the update's memory traffic overlaps finalize's dependent chains.
+#if !defined(PPE_TU_FLOW_SMALL)
 template <int BLOCK>
 __global__ __launch_bounds__(BLOCK) void ppe_flow_post_kernel(ppe_flow_kargs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t usm[];
@@ -2420,6 +2436,64 @@ __global__ __launch_bounds__(BLOCK) void ppe_flow_post_attack_kernel(ppe_flow_ka
     if (blockIdx.x < a.fin_wgs) flow_finalize_wg<BLOCK, true>(a, a.fin_wgs);
     else flow_update_wg<BLOCK>(a, blockIdx.x - a.fin_wgs, usm);
 }
+#else
+// One launch for a small flow batch (csrc/ppe_kernels_flow_small.hip; 1 <= n <= PPE_FLOW_SMALL_CUTOFF,
+// ppe_pick_flow_small): one workgroup of 1024 threads runs the FLOW classify body, then finalize with nwg = 1, instead
+// of two dependent launches sized for 1M-packet batches.
+//   classify   classify_body<FLOW> with flow.upd_wgs = 0: a found packet's FlowUpdate is flow_account's direct form (one
+//              memory-side atomic on the packed word and the last-seen store); no owner buckets, no update workgroups;
+//              the launch's completion word (done_cnt / done_host) is written at the body's end, behind its last image
+//              read, as in the classify launch;
+//   between    every wave drains its stores (vmcnt 0), the workgroup barrier, then an agent-scope acquire-release fence
+//              in every wave: what this CU's L1 holds from the classify phase is dropped before finalize reads;
+//   finalize   flow_finalize_wg<1024> with nwg = 1 over LDS taken from the classify phase's key slots (free behind
+//              the barrier): the overflow check and revoke, final verdicts, FlowAdd, compaction, counters.
+// Per word, what the finalize phase reads and how (MI355X_MICROARCH.md "Stale without an agent-scope acquire"):
+//   keys[]       FlowFind pulled key segments into L1 with plain loads; the claims then changed state words by CAS in
+//                L2, which does not refresh an L1 line.  flow_find_claim's probes are plain loads behind the fence: they
+//                miss L1 and read L2.  Finalize's own key stores (LIVE / TOMB) are read by nobody in this launch;
+//   creator[]    written by atomicMin in L2 (claim); read by plain loads behind the fence, by agent-scope atomic loads
+//                on the revoke path, whose stores (flow_revoke) are agent-scope atomic stores behind a barrier;
+//   rec[], rslot[], tile_miss[], miss_tiles[], verdict[], hit[]   plain (verdict: non-temporal) stores of the classify
+//                phase, drained before the barrier; plain loads behind the fence;
+//   tile_new[]   written and read inside finalize, with its own drain, barrier and release / acquire pair;
+//   ctl[]        every access is an agent-scope atomic (L2).
+// With one workgroup, finalize's arrive-and-poll pair around flow_revoke is workgroup 0 with itself: thread 0 adds its
+// arrival to ARRIVE, then reads ARRIVE >= nwg = 1 at its first poll; the REVOKED_SEQ poll is the other workgroups'
+// branch and does not exist here.  So the kernel waits on no other workgroup and has no unbounded loop (the poll is
+// bounded as it is in the post kernel, and passes at once).
+template <int MODE>
+__global__ __launch_bounds__(PPE_FLOW_SMALL_BLOCK) void ppe_flow_small_kernel(ppe_flow_small_kargs a) {
+    constexpr int BLOCK = PPE_FLOW_SMALL_BLOCK;
+    static_assert(sizeof(ppe_flow_small_kargs) <= 4096u, "HIP's limit for a kernel's explicit arguments");
+    static_assert(offsetof(ppe_flow_small_kargs, k) == 0u, "the classify arguments first, at ppe_kargs' own offsets");
+    classify_body<MODE, PF_HOIST, BLOCK, true>(a.k);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");
+    // finalize's LDS: the first words of the key slots
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    using L = Lds<BLOCK, true, 0u>;
+    static_assert(4u * (PPE_NBINS + 32u + BLOCK + 8u) <= L::KEYB, "finalize's arrays fit the key slots");
+    uint32_t *bins = smem, *lcnt = bins + PPE_NBINS, *part = lcnt + 32u, *tail = part + BLOCK;
+    ppe_flow_kargs f = {};
+    f.f = a.k.flow;
+    f.len = a.t.len;
+    f.verdict = a.t.verdict;
+    f.hit = a.t.hit;
+    f.fw_idx = a.t.fw_idx;
+    f.drop_idx = a.t.drop_idx;
+    f.tile_cnt = a.t.tile_cnt;
+    f.part8 = a.t.part8;
+    f.n = a.k.batch[0].n;
+    f.unsup_fw = a.k.unsup_fw;
+    f.now = a.k.now;
+    f.revoke = a.t.revoke;
+    f.fin_wgs = 1u;
+    f.cslots = a.k.cslots;
+    flow_finalize_wg<BLOCK>(f, 1u, bins, lcnt, part, tail[0], *(unsigned long long *)(tail + 2), tail + 4);
+}
+#endif
 
 // FlowTimeOut + FlowAgeTimeoutCB (flow.c:391-467): live flows idle for more than `timeout` become tombstones.
 template <int BLOCK>
@@ -2721,6 +2795,26 @@ extern "C" int ppe_launch_classify_attack_flow(const ppe_kargs *a, uint32_t grid
 extern "C" int ppe_launch_flow_post_attack(const ppe_flow_kargs *a, uint32_t grid, size_t shmem, void *stream) {
     hipLaunchKernelGGL(ppe_flow_post_attack_kernel<PPE_FLOW_POST_BLOCK>, dim3(grid), dim3(PPE_FLOW_POST_BLOCK), shmem,
                        (hipStream_t)stream, *a);
+    return (int)hipGetLastError();
+}
+#elif defined(PPE_TU_FLOW_SMALL)
+// csrc/ppe_kernels_flow_small.hip: this file again, exporting only the one-launch kernel for small flow batches over
+// the three image placements of the flow-table plan, at 1024 threads
+extern "C" int ppe_launch_flow_small(const ppe_kargs *a, const ppe_flow_small_tail *t, int mode, void *stream,
+                                     void *ev_start, void *ev_stop) {
+    const hipStream_t s = (hipStream_t)stream;
+    const hipEvent_t e0 = (hipEvent_t)ev_start, e1 = (hipEvent_t)ev_stop;
+    if (a->flow.upd_wgs != 0u || a->nbatch != 1u || a->ring) return (int)hipErrorInvalidValue;
+    ppe_flow_small_kargs k;
+    k.k = *a;
+    k.t = *t;
+    // the classify kernel's LDS at this block size (key slots, bins, bucket cursors, the staged image)
+    const size_t base = ppe_classify_fixed_lds(PPE_FLOW_SMALL_BLOCK, PF_HOIST, mode) + ppe_flow_lds_extra();
+    const size_t shmem = mode == IMG_GLOBAL ? base : base + (((size_t)a->stage_words * 4u + 1023u) & ~(size_t)1023u);
+    const dim3 g(1), b(PPE_FLOW_SMALL_BLOCK);
+    if (mode == IMG_LDS) hipExtLaunchKernelGGL(ppe_flow_small_kernel<IMG_LDS>, g, b, shmem, s, e0, e1, 0, k);
+    else if (mode == IMG_SPLIT) hipExtLaunchKernelGGL(ppe_flow_small_kernel<IMG_SPLIT>, g, b, shmem, s, e0, e1, 0, k);
+    else hipExtLaunchKernelGGL(ppe_flow_small_kernel<IMG_GLOBAL>, g, b, shmem, s, e0, e1, 0, k);
     return (int)hipGetLastError();
 }
 #elif defined(PPE_TU_STREAM)

@@ -166,6 +166,45 @@ class Engine:
         self._check(self.lib.ppe_classify_flow(self.ctx, C.byref(b), C.byref(r), C.byref(cfg or self.cfg()),
                                                s.cuda_stream), "ppe_classify_flow")
 
+    def classify_flow_host(self, hdr, lens, ts=None, cfg: abi.Cfg | None = None, chunk: int = 0,
+                           outputs=("verdict", "flow_hash", "acl_hit", "tuple"), out: dict | None = None) -> dict:
+        """ppe_classify_flow_host: FlowHandlePacket for a host-resident batch, in chunks through one stream in order
+        (one core's results whatever `chunk` is).  hdr (n, stride) uint8, lens, ts: numpy arrays (staged copies), or
+        pinned torch CPU tensors together with `out` (name -> pinned tensor), which the kernels then read and write
+        directly when the batch fits the table's max_batch."""
+        if out is not None:  # caller-owned buffers (pinned torch tensors)
+            ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+            n, stride = hdr.shape
+            b = abi.Batch(ptr(hdr), ptr(lens), ptr(ts), int(n), int(stride))
+            r = abi.Result(ptr(out.get("verdict")), ptr(out.get("flow_hash")), ptr(out.get("acl_hit")),
+                           ptr(out.get("fw_idx")), ptr(out.get("drop_idx")), ptr(out.get("tile_cnt")),
+                           ptr(out.get("tuple")), ptr(out.get("part8")), ptr(out.get("packed")))
+            res = out
+        else:
+            hdr = np.ascontiguousarray(hdr, dtype=np.uint8)
+            lens = np.ascontiguousarray(lens, dtype=np.uint32)
+            n, stride = hdr.shape
+            shapes = {"verdict": (n, np.uint32), "flow_hash": (n, np.uint32), "acl_hit": (n, np.int32),
+                      "tuple": ((n, 4), np.uint32), "fw_idx": (n, np.uint32), "drop_idx": (n, np.uint32),
+                      "tile_cnt": ((n + 63) // 64, np.uint32), "part8": (n, np.uint8), "packed": (n, np.uint64)}
+            res = {k: np.zeros(*shapes[k]) for k in outputs}
+            if ts is not None:
+                ts = np.ascontiguousarray(ts, dtype=np.uint64)
+            g = lambda k: res[k].ctypes.data if k in res else None  # noqa: E731
+            b = abi.Batch(hdr.ctypes.data, lens.ctypes.data, ts.ctypes.data if ts is not None else None, n, stride)
+            r = abi.Result(g("verdict"), g("flow_hash"), g("acl_hit"), g("fw_idx"), g("drop_idx"), g("tile_cnt"),
+                           g("tuple"), g("part8"), g("packed"))
+        rc = self.lib.ppe_classify_flow_host(self.ctx, C.byref(b), C.byref(r), C.byref(cfg or self.cfg()), int(chunk))
+        self._check(rc, "ppe_classify_flow_host")
+        return res
+
+    def flow_launch_info(self) -> tuple:
+        """ppe_flow_launch_info: (kind, launches) of the last flow batch: (1, 1) the one-launch kernel, (0, 2) the two
+        launches, (0, 0) before the first."""
+        k, n = C.c_uint32(9), C.c_uint32(9)
+        self._check(self.lib.ppe_flow_launch_info(self.ctx, C.byref(k), C.byref(n)), "ppe_flow_launch_info")
+        return k.value, n.value
+
     def flow_age(self, now: int, timeout: int = 20) -> int:
         d = C.c_uint64(0)
         self._check(self.lib.ppe_flow_age(self.ctx, int(now), int(timeout), C.byref(d)), "ppe_flow_age")
