@@ -177,11 +177,22 @@ struct ppe_portscan_table *DP_PortScan_Table(void);
  * neither.  There is no host flow object: m->flow stays as it was.  The table is read through the shim's context:
  * ppe_flow_info / ppe_flow_dump / ppe_format_flow_stat on ppe_compat_ctx().  Setting flow_able back to 0 keeps the
  * table and its flows; DP_Acl_Rule_Release destroys it with the context.
- * flow_able == 1 together with portscan_able == 1 or stream_tcp_track_enable is not built (the detector on flow misses
- * only; the TCP session machine): the flush fails with PPE_ENOTSUP before any state changes and every mbuf of the
- * burst goes to the drop hook, as for any classify step that cannot run. */
+ * flow_able == 1 together with portscan_able == 1 or stream_tcp_track_enable is refused (portscan_able is the stateless
+ * path's switch, every packet a miss; the flow table's detector is flow_portscan_able below; the TCP session machine is
+ * not built): the flush fails with PPE_ENOTSUP before any state changes and every mbuf of the burst goes to the drop
+ * hook, as for any classify step that cannot run. */
 extern uint32_t flow_able;
 extern uint32_t flow_item_num;
+/* The port-scan detector on the flow table's misses (PortScan_Detect inside FlowGetFlowFromHash, flow.c:196-243: after
+ * syn_check, before the ACL; a packet that finds its flow never reaches it), read per classify call.  Start value 0.
+ * With flow_able == 1, flow_portscan_able == 1, portscan_able == 0 and stream tracking off, the first flush creates the
+ * shim's port-scan table (the one portscan_able uses, 100,000 records) and attaches it to the flow table's path
+ * (ppe_flow_portscan_attach, ppe_hip.h); every flush takes portscan_action, portscan_exception_freq, flood_hold_time and
+ * DP_PortScan_Clock's values and goes through ppe_classify_flow_host.  DP_PortScan_Age and DP_PortScan_Table work on
+ * that table.  A packet the detector drops (PPE_ST_PORTSCAN_DROP) goes to the drop hook without DP_Log_Func, without
+ * PKT_HAS_FLOW and without a direction flag.  With flow_able == 0 it has no effect.  Setting it back to 0 detaches the
+ * table and keeps its records. */
+extern uint32_t flow_portscan_able;
 /* FLOW_UPDATE_TIMESTAMP's clock (seconds) for the bursts flushed afterwards, by value.  Starts at 0; with
  * flow_able == 0 the classify calls keep now_seconds = 0. */
 void DP_Flow_Clock(uint64_t now_seconds);

@@ -43,7 +43,7 @@ extern "C" {
  * detector (ppe_portscan_*, status 24, ppe_format_pkt_stat_ps, ppe_format_fw_config), off until a table is attached;
  * the land / SYN-flood / UDP-flood monitors (ppe_attack_*, statuses 25-28, ppe_format_attack_stat,
  * ppe_format_pkt_stat_atk), off until an object is attached; ppe_classify_host_ordered and
- * ppe_portscan_prepass_info; ppe_classify_flow_host and ppe_flow_launch_info */
+ * ppe_portscan_prepass_info; ppe_classify_flow_host and ppe_flow_launch_info; ppe_flow_portscan_attach, _max, _rounds */
 #define PPE_ABI_VERSION 8
 
 /* error codes (negative return values) */
@@ -434,13 +434,18 @@ int  ppe_classify_flow(ppe_ctx_t *ctx, const ppe_batch_t *in, const ppe_result_t
  * When every buffer is pinned and device-mapped, n <= max_batch and PPE_HOST_ZEROCOPY is not 0, the kernels read and
  * write the host buffers directly: one flow batch, no staging copy.
  * PPE_ENOTSUP before touching anything: wherever ppe_classify_flow refuses (stream tracking on, a port-scan table
- * attached, an object attached with ppe_attack_attach), and with an object attached with ppe_flow_attack_attach (its
- * per-batch port array does not map onto chunks).  A broken table: PPE_EIO, as ppe_classify_flow.
+ * attached with ppe_portscan_attach, an object attached with ppe_attack_attach), and with an object attached with
+ * ppe_flow_attack_attach (its per-batch port array does not map onto chunks).  A broken table: PPE_EIO, as
+ * ppe_classify_flow.
+ * With a port-scan table flow-attached and its detector on (ppe_flow_portscan_attach, able 1) the chunk is clamped to a
+ * multiple of 64 of at most ppe_flow_portscan_max() as well, batch.ts is taken per chunk, and the zero-copy form
+ * applies when n <= ppe_flow_portscan_max(); the result is still one core's run of the whole batch, whatever the chunk.
  * Flow batches submitted earlier on other streams must have completed (the internal stream does not wait for them). */
 int  ppe_classify_flow_host(ppe_ctx_t *ctx, const ppe_batch_t *in, const ppe_result_t *out, const ppe_cfg_t *cfg,
                             uint32_t chunk);
-/* What the last flow batch of the context's table took: *kind 1 and *launches 1 (the one-launch kernel), or 0 and 2;
- * 0 and 0 before the first batch.  NULL arguments: PPE_EINVAL. */
+/* What the last flow batch of the context's table took: *kind 1 and *launches 1 (the one-launch kernel), 2 and 1 (the
+ * one-launch kernel with the port-scan detector inside, ppe_flow_portscan_attach), or 0 and 2; 0 and 0 before the first
+ * batch.  NULL arguments: PPE_EINVAL. */
 int  ppe_flow_launch_info(ppe_ctx_t *ctx, uint32_t *kind, uint32_t *launches);
 /* FlowAgeTimeoutCB: delete flows with now > last_seen && now - last_seen > timeout_seconds; *deleted = count
  * (may be NULL).  Synchronises. */
@@ -584,8 +589,9 @@ int  ppe_defrag_info(ppe_defrag_t *d, ppe_defrag_info_t *info);      /* synchron
  * enqueued after it (by value, no synchronisation); rate (oct_cpu_rate) is cycles_per_second.
  * With a table attached and able = 1 every classify call of the context must go through one stream (or be ordered by
  * the caller), and ppe_classify_flow and ppe_classify_host return PPE_ENOTSUP before touching anything (the first:
- * whether a packet is a miss depends on earlier packets' verdicts; the second: its chunks run on several streams;
- * ppe_classify_host_ordered is the host-buffer call that runs the detector).
+ * the flow-table path calls the detector on flow misses only and has an attachment point of its own,
+ * ppe_flow_portscan_attach below; the second: its chunks run on several streams; ppe_classify_host_ordered is the
+ * host-buffer call that runs the detector).
  * The pre-pass of a batch of at most 2,048 packets is one kernel launch of one workgroup; a larger batch takes the
  * staged launches (ten, and more sort passes above 2,048 keys).  Both leave the same verdicts, counters and records.
  * PPE_PS_FUSED=0 in the environment at ppe_portscan_create gives a table that always takes the staged launches.
@@ -636,6 +642,37 @@ int  ppe_portscan_dump(ppe_portscan_t *ps, ppe_portscan_entry_t *entries, uint32
  * *launches the kernel launches it made (0 before the first batch).  Either pointer may be NULL.  No synchronisation. */
 int  ppe_portscan_prepass_info(ppe_portscan_t *ps, uint32_t *kind, uint32_t *launches);
 const char *ppe_portscan_last_error(ppe_portscan_t *ps);
+
+/* ---- Port-scan detector on the flow-table path (flow.c:196-243) ----
+ * The flow-table path's attachment point for the same table: with a table flow-attached and able = 1, ppe_classify_flow
+ * and ppe_classify_flow_host run FlowGetFlowFromHash with PortScan_Detect inside, exactly as one core running the batch
+ * in index order against both tables as the earlier packets left them:
+ *   - a packet that finds its flow (in the table, or created by an earlier packet of the batch) is forwarded and
+ *     accounted as without the detector and never reaches it: no record, no cycle stamp, no result count, even when
+ *     its source is held;
+ *   - a miss that fails syn_check is PPE_ST_FLOW_TCP_NO_SYN_FIRST, the detector is not called;
+ *   - every other miss calls PortScan_Detect (the semantics above: its own sip and dport, batch.ts[i] or
+ *     cfg->now_seconds, the table's clock; a record-less source gets a record at its first call while live < capacity,
+ *     else that call and every later one of the source in the batch are NOMEM);
+ *   - a result other than OK with action 0 is PPE_ST_PORTSCAN_DROP as the stateless path emits and counts it (acl_hit
+ *     -1, PPE_F_ACL clear, flow hash and tuple kept; the RX_OK chain, FLOW_PROC_FAIL, OUT_DROP, the table's drop): no
+ *     flow, no PPE_F_FLOW / NEWFLOW / TOCLIENT; with action 1 the state still runs and the packet goes on;
+ *   - then the ACL's verdict: DROP is ACL_DROP with no flow, FW creates the flow (FlowAdd) or is PPE_ST_FLOW_NOMEM.
+ * So a flow's creator is the lowest-index packet of its 5-tuple (either direction) that misses, passes syn_check, is
+ * not dropped by the detector, is forwarded by the ACL and finds pool room.
+ * One batch takes at most ppe_flow_portscan_max() packets (one launch of one workgroup, ppe_flow_launch_info kind 2);
+ * a larger device batch returns PPE_ENOTSUP before anything is touched (ppe_classify_flow_host chunks host batches of
+ * any size); n above the port-scan table's max_batch: PPE_EINVAL.  Also PPE_ENOTSUP before anything is touched: attack
+ * monitors flow-attached at the same time, and stream tracking.  With able = 0 or nothing flow-attached the flow path is
+ * byte for byte what it is without this interface, at every size.  The stateless calls do not see a flow-attached table.
+ * A table sits on at most one of the two attachment points: attaching one that the other point holds is PPE_EINVAL
+ * (detach first), as is a table of another context; ppe_portscan_destroy detaches from whichever holds it. */
+int  ppe_flow_portscan_attach(ppe_ctx_t *ctx, ppe_portscan_t *ps);   /* NULL detaches */
+uint32_t ppe_flow_portscan_max(void);
+/* Debug count (tools/ab_flow_portscan.py): the resolve rounds of the last batch that took the kernel with the detector
+ * inside (0: none yet, or no packet of it was pending).  A plain flow batch (able 0, nothing flow-attached) does not
+ * change it: check ppe_flow_launch_info for kind 2 first.  Synchronises. */
+int  ppe_flow_portscan_rounds(ppe_ctx_t *ctx, uint32_t *rounds);
 
 
 /* ---- Land, SYN-flood and UDP-flood monitors on the stateless classify path (dataplane/src/attack/dp_attack.c) ----

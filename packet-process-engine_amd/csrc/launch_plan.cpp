@@ -335,4 +335,13 @@ uint32_t ppe_pick_flow_small(uint32_t n, int small_allowed, int atk_flow_attache
     return (n >= 1u && n <= PPE_FLOW_SMALL_CUTOFF && small_allowed && !atk_flow_attached) ? 1u : 0u;
 }
 
+// the port-scan detector on the flow-table path (csrc/ppe_kernels_flow_portscan.hip): with a table flow-attached and its
+// detector on, a batch of up to one workgroup's worth of packets takes the kernel with the detector inside; a larger one
+// is refused (whether a packet reaches the detector depends on verdicts of earlier packets of the batch: a grid-wide form
+// is not built).  Nothing flow-attached, or portscan_able == 0 (dp_portscan.c:238): today's kernels at every size
+uint32_t ppe_pick_flow_portscan(uint32_t n, int flow_attached, uint32_t able) {
+    if (!flow_attached || able != 1u) return PPE_FPS_PLAIN;
+    return n <= PPE_FLOW_PS_MAX ? PPE_FPS_KERNEL : PPE_FPS_REFUSE;
+}
+
 }  // extern "C"

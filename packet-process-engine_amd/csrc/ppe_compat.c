@@ -43,6 +43,8 @@ uint32_t flood_hold_time = 600;
  * flow_able = 1 for the reference's behaviour.  flow_item_num: the pool (MEM_POOL_FLOW_NODE_NUM, mem_pool.h:72), read
  * when the table is created. */
 uint32_t flow_able = 0;
+/* PortScan_Detect on the flow table's misses (flow.c:215-230): off until set, with flow_able == 1 only (ppe_decode.h) */
+uint32_t flow_portscan_able = 0;
 uint32_t flow_item_num = 100000;
 PluginModule plugin_modules[PLUGIN_SIZE];
 
@@ -460,8 +462,9 @@ int DP_Flow_Age(uint64_t now_seconds, uint64_t *deleted) {
 
 /* PortScan_Detect behind Decode (flow.c:215-230), caller holds g_ctx_lock and g_ctx is set: the table on first use
  * (PORTSCAN_ITEM_NUM records; max_batch at least this burst: a later, larger burst goes through it in chunks), then
- * the globals and the clock by value for this burst, attached. */
-static int portscan_prepare_locked(uint32_t n) {
+ * the globals and the clock by value for this burst, attached: to the stateless path (portscan_able), or with flow_point
+ * to the flow table's (flow_portscan_able, the detector on flow misses). */
+static int portscan_prepare_locked(uint32_t n, int flow_point) {
     if (!g_ps) {
         ppe_portscan_cfg_t c = {1u, 0u, 50u, 600u, 100000u, 0u, 1000000000ull, 0u};
         c.max_batch = ((n > 4096u ? n : 4096u) + 63u) & ~63u;
@@ -474,7 +477,9 @@ static int portscan_prepare_locked(uint32_t n) {
     ppe_portscan_cfg_t v = {1u, portscan_action ? 1u : 0u, portscan_exception_freq, flood_hold_time, 0u, 0u, 0u, 0u};
     int rc = ppe_portscan_set(g_ps, &v);
     if (rc == PPE_OK) rc = ppe_portscan_clock(g_ps, g_ps_cycles, g_ps_seconds);
-    if (rc == PPE_OK) rc = ppe_portscan_attach(g_ctx, g_ps);
+    /* a table sits on one of the two attachment points: off the other first */
+    if (rc == PPE_OK) rc = flow_point ? ppe_portscan_attach(g_ctx, NULL) : ppe_flow_portscan_attach(g_ctx, NULL);
+    if (rc == PPE_OK) rc = flow_point ? ppe_flow_portscan_attach(g_ctx, g_ps) : ppe_portscan_attach(g_ctx, g_ps);
     return rc;
 }
 
@@ -532,19 +537,22 @@ static int classify_mbufs(mbuf_t **mb, uint32_t n) {
         sync_running_locked();
         if (flow_on) cfg.now_seconds = g_flow_now;  /* FLOW_UPDATE_TIMESTAMP's clock */
         if (g_ctx && flow_on && (portscan_able == 1u || stream_tcp_track_enable)) {
-            /* the detector on flow misses only and the TCP session machine are not built: the burst is refused before
-             * any state changes (ppe_decode.h) */
+            /* portscan_able is the stateless path's switch (the flow table's detector is flow_portscan_able) and the TCP
+             * session machine is not built: the burst is refused before any state changes (ppe_decode.h) */
             rc = PPE_ENOTSUP;
         } else {
             rc = g_ctx ? ppe_stream_tcp_set(g_ctx, &stcp) : PPE_ENODEV;
         }
         if (rc == PPE_OK && portscan_able == 1u) {  /* (dp_portscan.c:238: any other value is off) */
-            rc = portscan_prepare_locked(n);
+            rc = portscan_prepare_locked(n, 0);
             if (rc == PPE_OK) rc = ppe_classify_host_ordered(g_ctx, &b, &r, &cfg, 0);
         } else if (rc == PPE_OK) {
+            const int fps_on = flow_on && flow_portscan_able == 1u;  /* (without the flow table: no effect) */
             if (g_ps) rc = ppe_portscan_attach(g_ctx, NULL);  /* the table keeps its records while off */
+            if (rc == PPE_OK && g_ps && !fps_on) rc = ppe_flow_portscan_attach(g_ctx, NULL);
             if (rc == PPE_OK && flow_on) {  /* FlowHandlePacket: the table on first use, the burst in order through it */
                 rc = flow_prepare_locked(n);
+                if (rc == PPE_OK && fps_on) rc = portscan_prepare_locked(n, 1);  /* PortScan_Detect on its misses */
                 if (rc == PPE_OK) rc = ppe_classify_flow_host(g_ctx, &b, &r, &cfg, 0);
             } else if (rc == PPE_OK) {
                 rc = ppe_classify_host(g_ctx, &b, &r, &cfg, 0);

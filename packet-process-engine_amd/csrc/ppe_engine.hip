@@ -213,6 +213,7 @@ struct ppe_ctx {
     // / 8 / 32 groups 20.2 / 18.7 / 18.3 / 18.3 / 19.1 us (one run, tools/ab_bench.py)
     uint32_t max_groups = 8;
     ppe_portscan_table *ps = nullptr;  // ppe_portscan_attach
+    ppe_portscan_table *ps_flow = nullptr;  // ppe_flow_portscan_attach: ppe_classify_flow's detector (never the same table as ps)
     ppe_attack *atk = nullptr;         // ppe_attack_attach
     ppe_attack *atk_flow = nullptr;    // ppe_flow_attack_attach: ppe_classify_flow's monitors (never the same object as atk)
     FlowTable *flow = nullptr;  // ppe_flow_create
@@ -561,6 +562,23 @@ int ps_rebuild(ppe_portscan_table *t, int age, uint64_t now_cycles) {
     return PPE_OK;
 }
 
+// Room for the keys a batch of n packets may claim: keys in use never reach 3/4 of the slots: the bound first, then the
+// count, then a rebuild without aging
+int ps_reserve_keys(ppe_portscan_table *t, uint32_t n) {
+    if (t->occ_ub + n > (uint64_t)t->nslots / 4u * 3u) {
+        PSCHK(t, hipDeviceSynchronize());
+        unsigned long long occ = 0;
+        PSCHK(t, hipMemcpy(&occ, t->ctl + PPE_PSC_OCC, 8, hipMemcpyDeviceToHost));
+        t->occ_ub = occ;
+        if (t->occ_ub + n > (uint64_t)t->nslots / 4u * 3u) {
+            const int rc = ps_rebuild(t, 0, 0);
+            if (rc != PPE_OK) return rc;
+        }
+    }
+    t->occ_ub += n;
+    return PPE_OK;
+}
+
 // PortScan_Detect for batches in[0, nb) in order on stream s (csrc/ppe_portscan.hip), their drop masks one after the
 // other in t->mask
 int ps_prepass(ppe_ctx *c, const ppe_batch_t *in, uint32_t nb, const ppe_cfg_t *cfg, hipStream_t s,
@@ -584,18 +602,8 @@ int ps_prepass(ppe_ctx *c, const ppe_batch_t *in, uint32_t nb, const ppe_cfg_t *
     size_t off = 0;
     for (uint32_t i = 0; i < nb; ++i) {
         const uint32_t n = in[i].n;
-        // keys in use never reach 3/4 of the slots: the bound first, then the count, then a rebuild without aging
-        if (t->occ_ub + n > (uint64_t)t->nslots / 4u * 3u) {
-            PSCHK(t, hipDeviceSynchronize());
-            unsigned long long occ = 0;
-            PSCHK(t, hipMemcpy(&occ, t->ctl + PPE_PSC_OCC, 8, hipMemcpyDeviceToHost));
-            t->occ_ub = occ;
-            if (t->occ_ub + n > (uint64_t)t->nslots / 4u * 3u) {
-                const int rc = ps_rebuild(t, 0, 0);
-                if (rc != PPE_OK) return rc;
-            }
-        }
-        t->occ_ub += n;
+        const int krc = ps_reserve_keys(t, n);
+        if (krc != PPE_OK) return krc;
         ppe_ps_kargs a;
         ps_table_args(*t, a);
         a.hdr = in[i].hdr;
@@ -659,10 +667,11 @@ int ps_prepass(ppe_ctx *c, const ppe_batch_t *in, uint32_t nb, const ppe_cfg_t *
 // One launch over batches in[0..nb) (nb <= PPE_MAX_RING, each n > 0): every wave takes its tiles of batch 0, then
 // of batch 1, ... (no barrier between batches, one image staging for all of them).
 // small (flow-table launches only): the one-launch kernel of one 1024-thread workgroup, classify then finalize, with
-// finalize's own arguments
+// finalize's own arguments; with fps, the one-launch kernel with the port-scan detector inside and its arguments
 int launch(ppe_ctx *c, const ppe_batch_t *in, const ppe_result_t *out, uint32_t nb, const ppe_cfg_t *cfg,
            hipStream_t s, int slot_set, uint32_t idx_base = 0, const ppe_flowdev *fl = nullptr,
-           uint32_t *grid_out = nullptr, uint32_t atk_pbase = 0, const ppe_flow_small_tail *small = nullptr) {
+           uint32_t *grid_out = nullptr, uint32_t atk_pbase = 0, const ppe_flow_small_tail *small = nullptr,
+           const ppe_ps_kargs *fps = nullptr) {
     const int r = c->running;
     const ppe_plan &plan = c->plan[r][fl != nullptr];
     ppe_kargs a;
@@ -746,9 +755,10 @@ int launch(ppe_ctx *c, const ppe_batch_t *in, const ppe_result_t *out, uint32_t 
     }
     rc = track_launch(c, grid, a);
     if (rc != PPE_OK) return rc;
-    rc = small ? ppe_launch_flow_small(&a, small, (int)plan.mode, (void *)s, (void *)e0, (void *)e1)
-               : ppe_launch_classify(&a, grid, (int)plan.mode, (int)plan.pipe, (int)plan.block, fl != nullptr, (void *)s,
-                                     (void *)e0, (void *)e1);
+    rc = fps     ? ppe_launch_flow_portscan(&a, small, fps, (int)plan.mode, (void *)s, (void *)e0, (void *)e1)
+         : small ? ppe_launch_flow_small(&a, small, (int)plan.mode, (void *)s, (void *)e0, (void *)e1)
+                 : ppe_launch_classify(&a, grid, (int)plan.mode, (int)plan.pipe, (int)plan.block, fl != nullptr,
+                                       (void *)s, (void *)e0, (void *)e1);
     if (rc != 0) {
         untrack_launch(c, grid, a);
         return fail(c, PPE_EIO, "kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
@@ -1451,6 +1461,7 @@ int ppe_portscan_destroy(ppe_portscan_t *t) {
     (void)hipSetDevice(t->ctx->device);
     (void)hipDeviceSynchronize();
     if (t->ctx->ps == t) t->ctx->ps = nullptr;
+    if (t->ctx->ps_flow == t) t->ctx->ps_flow = nullptr;
     ps_free(t);
     return PPE_OK;
 }
@@ -1458,9 +1469,24 @@ int ppe_portscan_destroy(ppe_portscan_t *t) {
 int ppe_portscan_attach(ppe_ctx_t *c, ppe_portscan_t *t) {
     if (!c) return PPE_EINVAL;
     if (t && t->ctx != c) return fail(c, PPE_EINVAL, "ppe_portscan_attach: the table belongs to another context");
+    if (t && c->ps_flow == t)
+        return fail(c, PPE_EINVAL, "ppe_portscan_attach: the table is attached with ppe_flow_portscan_attach: detach first");
     c->ps = t;
     return PPE_OK;
 }
+
+// The flow-table path's attachment point: the same table and detector, called on flow misses only (flow.c:196-230), so
+// a table runs under one of the two
+int ppe_flow_portscan_attach(ppe_ctx_t *c, ppe_portscan_t *t) {
+    if (!c) return PPE_EINVAL;
+    if (t && t->ctx != c) return fail(c, PPE_EINVAL, "ppe_flow_portscan_attach: the table belongs to another context");
+    if (t && c->ps == t)
+        return fail(c, PPE_EINVAL, "ppe_flow_portscan_attach: the table is attached with ppe_portscan_attach: detach first");
+    c->ps_flow = t;
+    return PPE_OK;
+}
+
+uint32_t ppe_flow_portscan_max(void) { return PPE_FLOW_PS_MAX; }
 
 int ppe_portscan_clock(ppe_portscan_t *t, uint64_t now_cycles, uint64_t now_seconds) {
     if (!t) return PPE_EINVAL;
@@ -2085,8 +2111,8 @@ int ppe_classify_flow(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *o
     if (!out->verdict) return fail(c, PPE_EINVAL, "ppe_classify_flow needs the verdict output");
     // later packets of a tracked flow need the TCP session state machine (stream-tcp.c:3005-3140): not built
     if (c->stcp.track) return fail(c, PPE_ENOTSUP, "ppe_classify_flow with stream tracking on is not supported");
-    // PortScan_Detect runs on flow misses only (flow.c:196-215), and whether a packet misses depends on the verdicts
-    // of the packets before it: not built
+    // PortScan_Detect runs on flow misses only (flow.c:196-215): a table attached for the stateless path would see every
+    // packet; the flow path's detector takes ppe_flow_portscan_attach
     if (c->ps) return fail(c, PPE_ENOTSUP, "ppe_classify_flow with a port-scan table attached is not supported");
     // an object attached for the stateless path counts every forwarded SYN in syncount_accum; here it counts flow
     // creations (FlowAdd): that takes ppe_flow_attack_attach
@@ -2095,6 +2121,22 @@ int ppe_classify_flow(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *o
     if (rc != PPE_OK || in->n == 0) return rc;
     FlowTable &t = *c->flow;
     if (in->n > t.max_batch) return fail(c, PPE_EINVAL, "batch larger than the flow table's max_batch");
+    // the detector on flow misses (a table flow-attached, portscan_able 1): one launch of one workgroup, up to
+    // PPE_FLOW_PS_MAX packets; refused before anything is touched otherwise
+    ppe_portscan_table *pt = c->ps_flow;
+    const uint32_t fps = ppe_pick_flow_portscan(in->n, pt != nullptr, pt ? pt->cfg.able : 0u);
+    if (fps != PPE_FPS_PLAIN) {
+        if (c->atk_flow)
+            return fail(c, PPE_ENOTSUP, "ppe_classify_flow with a port-scan table and attack monitors both flow-attached "
+                                        "is not supported");
+        if (fps == PPE_FPS_REFUSE)
+            return fail(c, PPE_ENOTSUP, "ppe_classify_flow with a port-scan table flow-attached takes at most %u packets "
+                                        "per batch (ppe_flow_portscan_max; ppe_classify_flow_host chunks larger ones)",
+                        PPE_FLOW_PS_MAX);
+        if (in->n > pt->cfg.max_batch)
+            return fail(c, PPE_EINVAL, "batch of %u packets exceeds the port-scan table's max_batch %u", in->n,
+                        pt->cfg.max_batch);
+    }
     HIPCHK(c, use_device(c));
     flow_apply_snapshot(t);
     if (t.tomb_ub > t.nslots / 4u && t.snap_used + 1u < t.batches) {
@@ -2120,12 +2162,34 @@ int ppe_classify_flow(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *o
     if (t.use_event) HIPCHK(c, hipEventRecord(t.pre_launch, s));
     // (the same for both launch shapes: the host's bounds, the snapshot ring and the parity follow the batch)
     const bool may_overflow = t.live_ub + in->n > t.capacity;
+    // (with the detector, a claim whose claimers were all dropped leaves a tombstone too)
+    const bool may_tomb = may_overflow || fps == PPE_FPS_KERNEL;
     // a small batch: classify and finalize in one launch of one workgroup, the found flows' updates by the direct
     // atomics (no owner buckets, no update workgroups).  Not with monitors flow-attached (their syncount count lives
     // in the post kernel), not while the post-launch failure hook is armed
-    const bool small = ppe_pick_flow_small(in->n, t.small_allowed && __atomic_load_n(&g_fail_post, __ATOMIC_RELAXED) == 0u,
+    const bool small = fps != PPE_FPS_KERNEL &&
+                       ppe_pick_flow_small(in->n, t.small_allowed && __atomic_load_n(&g_fail_post, __ATOMIC_RELAXED) == 0u,
                                            c->atk_flow != nullptr) != 0u;
-    if (small) {
+    if (fps == PPE_FPS_KERNEL) {
+        rc = ps_reserve_keys(pt, in->n);  // (may synchronise and rebuild the detector's table; nothing enqueued yet)
+        if (rc != PPE_OK) return rc;
+        ppe_ps_kargs pa;
+        ps_table_args(*pt, pa);
+        pa.ts = in->ts;
+        pa.ts_default = cfg ? cfg->now_seconds : 0u;
+        pa.n = in->n;
+        pa.now_cycles = pt->now_cycles;
+        pa.now_seconds = pt->now_seconds;
+        pa.freq = pt->cfg.exception_freq;
+        pa.hold_seconds = pt->cfg.hold_seconds;
+        pa.action = pt->cfg.action;
+        ppe_flowdev ds = d;
+        ds.upd_wgs = 0;
+        const ppe_flow_small_tail tail = {in->len,      out->verdict, out->acl_hit, out->fw_idx, out->drop_idx,
+                                          out->tile_cnt, out->part8,  0u,           0u};
+        rc = launch(c, in, out, 1, cfg, s, 0, 0, &ds, nullptr, 0, &tail, &pa);
+        if (rc != PPE_OK) return rc;  // (nothing ran: both tables are as they were)
+    } else if (small) {
         ppe_flowdev ds = d;
         ds.upd_wgs = 0;
         const ppe_flow_small_tail tail = {in->len,      out->verdict, out->acl_hit, out->fw_idx, out->drop_idx,
@@ -2177,15 +2241,15 @@ int ppe_classify_flow(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *o
             }
         }
     }
-    t.last_kind = small ? 1u : 0u;
-    t.last_launches = small ? 1u : 2u;
+    t.last_kind = fps == PPE_FPS_KERNEL ? 2u : small ? 1u : 0u;
+    t.last_launches = (fps == PPE_FPS_KERNEL || small) ? 1u : 2u;
     t.cum_n[t.batches % FlowTable::kSnapRing] = t.tot_n;
     t.cum_rev[t.batches % FlowTable::kSnapRing] = t.tot_rev;
     t.tot_n += in->n;
-    if (may_overflow) t.tot_rev += in->n;
+    if (may_tomb) t.tot_rev += in->n;
     ++t.batches;
     t.live_ub = std::min<uint64_t>(t.live_ub + in->n, t.capacity);
-    if (may_overflow) t.tomb_ub += in->n;  // revoked claims leave tombstones
+    if (may_tomb) t.tomb_ub += in->n;  // revoked claims leave tombstones
     return PPE_OK;
 }
 
@@ -2208,13 +2272,19 @@ int ppe_classify_flow_host(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result
         return fail(c, PPE_ENOTSUP, "ppe_classify_flow_host with attack monitors flow-attached is not supported");
     int rc = check_batch(c, in, cfg);
     if (rc != PPE_OK || in->n == 0) return rc;
-    const uint32_t cmax = c->flow->max_batch & ~63u;
-    if (cmax < 64u) return fail(c, PPE_EINVAL, "ppe_classify_flow_host: the flow table's max_batch is below one tile");
+    // the detector on (a table flow-attached, portscan_able 1): chunks of at most PPE_FLOW_PS_MAX packets, each one launch
+    const bool fps = ppe_pick_flow_portscan(1u, c->ps_flow != nullptr, c->ps_flow ? c->ps_flow->cfg.able : 0u) != PPE_FPS_PLAIN;
+    const uint32_t bmax = fps ? std::min(c->flow->max_batch, std::min(c->ps_flow->cfg.max_batch, PPE_FLOW_PS_MAX))
+                              : c->flow->max_batch;
+    const uint32_t cmax = bmax & ~63u;
+    if (cmax < 64u)
+        return fail(c, PPE_EINVAL, "ppe_classify_flow_host: the %s table's max_batch is below one tile",
+                    (c->flow->max_batch & ~63u) < 64u ? "flow" : "port-scan");
     HIPCHK(c, use_device(c));
     if (!c->host_cs) HIPCHK(c, hipStreamCreateWithFlags(&c->host_cs, hipStreamNonBlocking));
     const hipStream_t s = c->host_cs;
     // Zero-copy: every buffer pinned and device-mapped, one batch: the kernels read and write the host buffers
-    if (env_int("PPE_HOST_ZEROCOPY", 1) && in->n <= c->flow->max_batch) {
+    if (env_int("PPE_HOST_ZEROCOPY", 1) && in->n <= bmax) {
         ppe_batch_t b = *in;
         ppe_result_t r = *out;
         bool ok = (b.hdr = (const uint8_t *)mapped_host(in->hdr)) && (b.len = (const uint32_t *)mapped_host(in->len));
@@ -2270,6 +2340,17 @@ int ppe_flow_launch_info(ppe_ctx_t *c, uint32_t *kind, uint32_t *launches) {
     if (const int u = flow_usable(c)) return u;
     *kind = c->flow->last_kind;
     *launches = c->flow->last_launches;
+    return PPE_OK;
+}
+
+int ppe_flow_portscan_rounds(ppe_ctx_t *c, uint32_t *rounds) {
+    if (!c || !rounds) return PPE_EINVAL;
+    if (const int u = flow_usable(c)) return u;
+    HIPCHK(c, use_device(c));
+    HIPCHK(c, hipDeviceSynchronize());
+    unsigned long long w = 0;
+    HIPCHK(c, hipMemcpy(&w, c->flow->ctl + PPE_FCTL_PS_ROUNDS, 8, hipMemcpyDeviceToHost));
+    *rounds = (uint32_t)w;
     return PPE_OK;
 }
 

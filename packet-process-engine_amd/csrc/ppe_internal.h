@@ -57,6 +57,8 @@ enum { PPE_FCTL_LIVE = 0, PPE_FCTL_NEW_FLOW, PPE_FCTL_DEL_FLOW, PPE_FCTL_BATCH_N
        PPE_FCTL_BATCH_NEW1,            /* BATCH_NEW of odd batches: the creators (slots claimed) the classify launch
                                           counts, by batch parity; finalize reads its batch's and zeroes the next's */
        PPE_FCTL_ARRIVE,                /* finalize, overflow batches: workgroups done marking their tiles' creators */
+       PPE_FCTL_PS_ROUNDS,             /* the last batch of the kernel with the port-scan detector inside: resolve rounds
+                                          taken (debug count, ppe_flow_portscan_rounds) */
        PPE_FCTL_WORDS = 16 };
 #define PPE_PK_SHIFT 40u                       /* packed counter: packets in bits 63:40, bytes in 39:0 */
 #define PPE_PK_FOLD_PKTS (1ull << 23)          /* fold into `stats` once either field reaches half its range */
@@ -348,6 +350,21 @@ enum { PPE_PS_K_FIND = 0, PPE_PS_K_CREATORS, PPE_PS_K_SCAN, PPE_PS_K_GRANT, PPE_
  * against the staged launches at 1 .. 2,048 packets */
 #define PPE_PS_FUSED_CUTOFF PPE_PS_SORT_BLOCK
 
+/* ---- the flow-table kernel with the port-scan detector inside (csrc/ppe_kernels_flow_portscan.hip) ----
+ * A flow batch of 1 <= n <= PPE_FLOW_PS_MAX packets of a context with a table flow-attached (ppe_flow_portscan_attach)
+ * and enabled: classify, resolve and finalize in one launch of one PPE_FLOW_PS_BLOCK-thread workgroup, one packet per
+ * thread.  One of 512 / 1,024 / 2,048; 2,048 needs two packets per thread and 80 KB of resolve state, more than the
+ * 42 KB of LDS the classify phase leaves free in front of every image placement. */
+#define PPE_FLOW_PS_MAX 1024u
+#define PPE_FLOW_PS_BLOCK 1024
+/* the arguments of the one-launch flow kernel, then the detector's: the table and the clock of ppe_ps_kargs (keys, recs,
+ * ctl, smask, capacity, ts, ts_default, now_cycles, now_seconds, rate, freq, hold_seconds, action; nothing else is read) */
+struct ppe_flow_ps_kargs {
+    struct ppe_kargs k;
+    struct ppe_flow_small_tail t;
+    struct ppe_ps_kargs ps;
+};
+
 /* flow-hash steering across GPUs (ppe_steer_partition / ppe_gather_rows / ppe_scatter_rows) */
 #define PPE_STEER_MAX_WORLD 16
 struct ppe_steer_kargs {
@@ -455,6 +472,11 @@ uint32_t ppe_pick_attack_flow(int flow, int flow_attached);
  * (small_allowed: not created under PPE_FLOW_SMALL=0, the post-launch failure hook not armed) and no monitors are
  * flow-attached (their syncount count lives in the post kernel); else 0, the two launches */
 uint32_t ppe_pick_flow_small(uint32_t n, int small_allowed, int atk_flow_attached);
+/* how a flow batch of n packets runs with respect to the port-scan detector: PPE_FPS_PLAIN today's kernels (no table
+ * flow-attached, or its detector off: portscan_able == 0), PPE_FPS_KERNEL the one-launch kernel with the detector
+ * inside (1 <= n <= PPE_FLOW_PS_MAX), PPE_FPS_REFUSE a larger batch (PPE_ENOTSUP before anything is touched) */
+enum { PPE_FPS_PLAIN = 0, PPE_FPS_KERNEL = 1, PPE_FPS_REFUSE = 2 };
+uint32_t ppe_pick_flow_portscan(uint32_t n, int flow_attached, uint32_t able);
 /* the monitors' set / tick / clear kernel (csrc/ppe_attack.hip), stream-ordered.  Returns hipError_t */
 int ppe_launch_attack_ctl(const struct ppe_atk_kargs *a, void *stream);
 /* one kernel of the port-scan pre-pass (csrc/ppe_portscan.hip), grid sized from the arguments.  Returns hipError_t */
@@ -471,6 +493,10 @@ int ppe_launch_flow(int kind, const struct ppe_flow_kargs *a, uint32_t grid, voi
  * PPE_FLOW_SMALL_BLOCK threads; a->flow.upd_wgs must be 0.  Returns hipError_t */
 int ppe_launch_flow_small(const struct ppe_kargs *a, const struct ppe_flow_small_tail *t, int mode, void *stream,
                           void *ev_start, void *ev_stop);
+/* the one-launch flow kernel with the port-scan detector inside (csrc/ppe_kernels_flow_portscan.hip): one workgroup of
+ * PPE_FLOW_PS_BLOCK threads, a->batch[0].n <= PPE_FLOW_PS_MAX; a->flow.upd_wgs must be 0.  Returns hipError_t */
+int ppe_launch_flow_portscan(const struct ppe_kargs *a, const struct ppe_flow_small_tail *t,
+                             const struct ppe_ps_kargs *ps, int mode, void *stream, void *ev_start, void *ev_stop);
 #define PPE_FLOW_BLOCK 256      /* flow kernels' workgroup size */
 /* steering: 0 count, 1 scan (one workgroup), 2 scatter the permutation; rows: gather / scatter of fixed rows */
 int ppe_launch_steer(int phase, const struct ppe_steer_kargs *a, uint32_t grid, void *stream);

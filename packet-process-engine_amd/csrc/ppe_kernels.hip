@@ -1415,12 +1415,12 @@ __device__ __forceinline__ void atk_count(uint32_t *bins, uint32_t flags) {
 // the decoders, ahead of FlowFind, so a packet they drop leaves decode() as a decode error does (no PPE_F_L4): no
 // lookup, no claim, no record, not a miss.  syncount_accum is not counted here: it counts the flows SYNs create,
 // which the post launch knows (flow_finalize_wg).
-// (csrc/ppe_kernels_flow_small.hip builds this body as a function, classify_body, the first phase of its one-launch
-// kernel, and has no ppe_classify_kernel: giving the body a function form that this kernel calls moved instructions in
+// (csrc/ppe_kernels_flow_small.hip and csrc/ppe_kernels_flow_portscan.hip build this body as a function, classify_body,
+// the first phase of their one-launch kernels, and have no ppe_classify_kernel: giving the body a function form that this kernel calls moved instructions in
 // it, DESIGN.md §5.10, so only the header differs and every other unit compiles the text it always did)
 template <int MODE, int PF, int BLOCK, bool FLOW, bool PART = false, bool STM = false, bool PSC = false,
           bool ATK = false>
-#if defined(PPE_TU_FLOW_SMALL)
+#if defined(PPE_TU_FLOW_SMALL) || defined(PPE_TU_FLOW_PS)
 __device__ __forceinline__ void classify_body(const ppe_kargs &a) {
 #else
 __global__ __launch_bounds__(BLOCK, (PF == PF_MULTI && !FLOW) ? PPE_MT_WAVES
@@ -2081,6 +2081,9 @@ __device__ __forceinline__ void flow_revoke(const ppe_flow_kargs &a, uint32_t *p
 // tile by ballot, summed per workgroup in LDS, one add per non-empty port into the workgroup's own count slot
 // (csrc/ppe_kernels_flow_small.hip: the same body over LDS its kernel provides, a part of the dynamic LDS whose layout
 // the classify phase fixes; nothing static may sit in front of that)
+// (csrc/ppe_kernels_flow_portscan.hip: ppe_flow_ps_kernel's finalize phase, below, emits a found packet, a creator, a
+// FLOW_NOMEM and a tombstone from its own per-thread decisions the way the loop here does: a change to what FlowAdd /
+// FlowUpdate emit belongs in both places)
 template <int BLOCK, bool ATK = false>
 #if defined(PPE_TU_FLOW_SMALL)
 __device__ __forceinline__ void flow_finalize_wg(const ppe_flow_kargs &a, uint32_t nwg, uint32_t *bins, uint32_t *lcnt,
@@ -2495,6 +2498,308 @@ __global__ __launch_bounds__(PPE_FLOW_SMALL_BLOCK) void ppe_flow_small_kernel(pp
 }
 #endif
 
+#if defined(PPE_TU_FLOW_PS)
+#include "ppe_portscan_dev.h"
+// One launch for a flow batch with the port-scan detector inside (csrc/ppe_kernels_flow_portscan.hip; a table attached
+// with ppe_flow_portscan_attach, portscan_able 1; 1 <= n <= PPE_FLOW_PS_MAX, ppe_pick_flow_portscan):
+// FlowGetFlowFromHash with PortScan_Detect on every flow miss, behind syn_check and ahead of the ACL's verdict
+// (flow.c:196-243), exactly as one core running the batch in index order.  One workgroup of 1024 threads, thread p owns
+// packet p from the resolve phase on.
+//   classify   classify_body<FLOW> with flow.upd_wgs = 0, as the one-launch kernel for small batches: found packets are
+//              final; a pending packet leaves its record, its provisional status (NO_SYN / ACL_DROP / ACL_FW) and, as a
+//              would-be creator, its claim;
+//   between    every wave drains its stores, the workgroup barrier, an agent-scope acquire-release fence in every wave;
+//   setup      a pending packet's tuple is named by the lowest-index claimer of its claimed slot (creator[], a packet
+//              index; none: no packet of the tuple can create it), its source, if it may reach the detector (ACL_DROP /
+//              ACL_FW), by the source's lowest-index such packet (firstinv of the key's slot, as the pre-pass finds first
+//              appearances); that packet's thread loads the source's record into LDS;
+//   resolve    rounds: every undecided packet enters its index in the minimum of its tuple (claimers only), of its source
+//              and of the batch; a packet is ready when no lower-index undecided claimer of its tuple exists (so whether
+//              it finds a flow created in this batch is known), no lower-index undecided packet of its source, and, only
+//              when a pool can run out in this batch, no lower-index undecided claimer (flow pool: live + claims >
+//              capacity) or detector candidate (record pool: live + candidates > capacity) at all.  Every ready packet
+//              decides: found; else syn_check's or the ACL's own verdict; in between PortScan_Detect on the source's LDS
+//              state (record granted at the source's first call while records are left, else NOMEM for the batch),
+//              status 24 for a result other than OK with action 0, and for an ACL_FW packet the creation of its flow or
+//              FLOW_NOMEM.  The lowest undecided index is always ready, so at most one round per pending packet; the loop
+//              is bounded by n + 1 rounds (overrun: PPE_FCTL_ERR, the undecided keep their provisional verdict) and its
+//              condition is an LDS word read behind a barrier.  No wait on another lane, no spin;
+//   finalize   each thread completes its packet from its decision (registers): FlowAdd / FlowUpdate, the verdict, the
+//              tile's compaction and the counters as flow_finalize_wg does them; the lowest claimer of a slot that ended
+//              without a creator turns it into a tombstone (counted); the sources' owners store their records back, with
+//              cycle = now for a source whose detector ran.
+// Uniqueness: a packet's decision reads only decisions of lower-index packets (its tuple's claimers, its source's
+// detector calls, the pools' earlier grants), each final before the packet is ready, so the rounds compute the one
+// solution of the index-order recursion whatever the order in which ready packets are taken.
+// Per word, what the later phases read and how:
+//   rec[], rslot[], tile_miss[], verdict[]   classify's plain / non-temporal stores, drained; plain loads behind the fence;
+//   keys[]       flow_find_claim's plain loads behind the fence (the claims' CASes do not refresh L1); nothing stores
+//                keys between the fence and the probes; finalize's LIVE / TOMB stores are read by nobody here;
+//   creator[]    atomicMin in L2 (claims); agent-scope atomic loads;
+//   detector keys     agent-scope CAS / atomic loads (ps_find_claim);
+//   firstinv, flags   one 64-bit word: firstinv by agent-scope fetch_max in setup, both halves read by agent-scope atomic
+//                loads behind a drain and a barrier; stored back plainly (firstinv 0) by the owner at the end;
+//   record words 0-3  plain loads by the owner in setup (no atomic touches them), plain stores at the end;
+//   ctl[] (both tables)   agent-scope atomics; the batch-parity resets are plain stores of words nobody reads here.
+enum { FPS_KEEP = 0, FPS_FOUND, FPS_CREATE, FPS_NOMEM, FPS_PSDROP };
+enum { FPG_ALL = 0, FPG_CLAIM, FPG_EMIN, FPG_NCREATED, FPG_GRANTED, FPG_OCC, FPG_ELIG, FPG_FTIGHT, FPG_ROOM, FPG_PSFREE,
+       FPG_CNT0 /* OK, NOMEM, DETECTED, HOLD, drop */, FPG_WORDS = 16 };
+constexpr uint32_t FPS_INF = 0xffffffffu;
+constexpr uint32_t FPS_NOREC = 0x20000u, FPS_STEPPED = 0x40000u;  // a source's LDS port word, beside PPE_PS_LIVE
+
+template <int MODE>
+__global__ __launch_bounds__(PPE_FLOW_PS_BLOCK) void ppe_flow_ps_kernel(ppe_flow_ps_kargs a) {
+    constexpr int BLOCK = PPE_FLOW_PS_BLOCK;
+    static_assert(sizeof(ppe_flow_ps_kargs) <= 4096u, "HIP's limit for a kernel's explicit arguments");
+    static_assert(offsetof(ppe_flow_ps_kargs, k) == 0u, "the classify arguments first, at ppe_kargs' own offsets");
+    static_assert(PPE_FLOW_PS_MAX <= (uint32_t)BLOCK, "one packet per thread");
+    classify_body<MODE, PF_HOIST, BLOCK, true>(a.k);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");
+    // LDS: what the classify phase had in front of the image (key slots, bins, owner buckets), free behind the barrier
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    using L = Lds<BLOCK, true, 4u * PPE_UPD_OWNERS * (1u + (PPE_UPD_LDS ? PPE_UPD_CAP : 0u))>;
+    static_assert(4u * (PPE_NBINS + 32u + 10u * BLOCK + FPG_WORDS) <= L::IMGB, "the resolve arrays fit in front of the image");
+    uint32_t *bins = smem, *lcnt = bins + PPE_NBINS;
+    uint32_t *tmin = lcnt + 32u, *smin = tmin + BLOCK, *created = smin + BLOCK;  // by tuple / source / tuple name
+    uint32_t *s_hold = created + BLOCK, *s_lc = s_hold + 2 * BLOCK;              // [2][BLOCK]: low, high words
+    uint32_t *s_ld = s_lc + 2 * BLOCK, *s_exc = s_ld + BLOCK, *s_lexc = s_exc + BLOCK, *g = s_lexc + BLOCK;
+    const ppe_flowdev &f = a.k.flow;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint32_t n = a.k.batch[0].n, ntiles = (n + 63u) >> 6, p = tid;
+    for (uint32_t i = tid; i < PPE_NBINS + 32u; i += BLOCK) bins[i] = 0;
+    if (tid < FPG_WORDS) g[tid] = 0;
+    tmin[p] = smin[p] = created[p] = FPS_INF;
+    __syncthreads();
+    if (tid == 0) {
+        // the pools as the batch starts (LIVE_AT_BATCH and the claim count: written by the classify phase)
+        const unsigned long long live = __hip_atomic_load(&f.ctl[PPE_FCTL_LIVE_AT_BATCH], __ATOMIC_RELAXED,
+                                                          __HIP_MEMORY_SCOPE_AGENT),
+                                 cr = __hip_atomic_load(&f.ctl[fctl_new(f.parity)], __ATOMIC_RELAXED,
+                                                        __HIP_MEMORY_SCOPE_AGENT),
+                                 pl = __hip_atomic_load(&a.ps.ctl[PPE_PSC_LIVE], __ATOMIC_RELAXED,
+                                                        __HIP_MEMORY_SCOPE_AGENT);
+        g[FPG_FTIGHT] = live + cr > f.capacity ? 1u : 0u;
+        g[FPG_ROOM] = f.capacity > live ? (uint32_t)(f.capacity - live) : 0u;
+        g[FPG_PSFREE] = a.ps.capacity > pl ? (uint32_t)(a.ps.capacity - pl) : 0u;
+        // the next batch's creator and miss-tile counters (last used by the previous batch, whose kernels have completed)
+        f.ctl[fctl_new(f.parity ^ 1u)] = 0;
+        f.ctl[PPE_FCTL_MISS0 + (f.parity ^ 1u)] = 0;
+    }
+    // ---- setup ----
+    const bool valid = p < n;
+    const uint64_t mask = wv < ntiles ? f.tile_miss[wv] : 0ull;
+    const bool pend = valid && ((mask >> lane) & 1ull);
+    const uint32_t v = valid ? a.t.verdict[p] : 0u;
+    uint4 r = make_uint4(0u, 0u, 0u, 0u);
+    uint32_t prov = 0, s = PPE_FLOW_NONE, trep = FPS_INF, srep = FPS_INF, pslot = PPE_PS_NOSLOT;
+    bool claimer = false, elig = false;
+    uint64_t ts = 0;
+    if (pend) {
+        r = ((const uint4 *)f.rec)[p];
+        prov = (r.w >> 8) & 0xffu;
+        claimer = prov == PPE_ST_ACL_FW;
+        elig = claimer || prov == PPE_ST_ACL_DROP;  // past syn_check: PortScan_Detect's candidates (flow.c:204-215)
+        s = claimer ? f.rslot[p] : flow_find_claim(f, r);
+        if (s != PPE_FLOW_NONE) {
+            trep = __hip_atomic_load(&f.creator[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (trep >= n) {  // (no claim of this batch on the slot: cannot be, the packet missed the table)
+                trep = FPS_INF;
+                s = PPE_FLOW_NONE;
+            }
+        }
+        if (elig) {
+            ts = a.ps.ts ? a.ps.ts[p] : a.ps.ts_default;  // mbuf->timestamp
+            atomicAdd(&g[FPG_ELIG], 1u);
+            bool claimed;
+            pslot = ps_find_claim(a.ps.keys, a.ps.smask, r.x, claimed);
+            if (claimed) atomicAdd(&g[FPG_OCC], 1u);
+            if (pslot != PPE_PS_NOSLOT)
+                __hip_atomic_fetch_max(&ps_rec32(a.ps.recs, pslot)[PS_W_FIRST], ~p, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    const bool ftight = g[FPG_FTIGHT] != 0u, rtight = g[FPG_ELIG] > g[FPG_PSFREE];
+    if (pslot != PPE_PS_NOSLOT) {
+        uint32_t *r32 = ps_rec32(a.ps.recs, pslot);
+        srep = ~__hip_atomic_load(&r32[PS_W_FIRST], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (srep > p) srep = FPS_INF;  // (cannot be: this packet entered its own index)
+        if (srep == p) {               // the source's first candidate: its record into LDS (none: pcb_create's zeroes)
+            const unsigned long long *rec = a.ps.recs + (size_t)pslot * PPE_PS_REC_WORDS;
+            const uint32_t fl = __hip_atomic_load(&r32[PS_W_FLAGS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const bool live = (fl & PPE_PS_LIVE) != 0u;
+            const unsigned long long lc = live ? rec[0] : 0ull, hold = live ? rec[2] : 0ull, ex = live ? rec[3] : 0ull;
+            s_lc[p] = (uint32_t)lc;
+            s_lc[BLOCK + p] = (uint32_t)(lc >> 32);
+            s_hold[p] = (uint32_t)hold;
+            s_hold[BLOCK + p] = (uint32_t)(hold >> 32);
+            s_exc[p] = (uint32_t)ex;
+            s_lexc[p] = (uint32_t)(ex >> 32);
+            s_ld[p] = live ? ((fl & 0xffffu) | PPE_PS_LIVE) : 0u;
+        }
+    }
+    // ---- resolve ----
+    bool und = pend;
+    uint32_t outc = FPS_KEEP, cidx = FPS_INF, rounds = 0;
+    for (uint32_t round = 0;; ++round) {
+        if (tid == 0) g[FPG_ALL] = g[FPG_CLAIM] = g[FPG_EMIN] = FPS_INF;
+        if (und && trep != FPS_INF) tmin[trep] = FPS_INF;  // (every undecided packet of the tuple, claimer or not)
+        if (und && srep != FPS_INF) smin[srep] = FPS_INF;
+        __syncthreads();
+        if (und) {
+            atomicMin(&g[FPG_ALL], p);
+            if (claimer) atomicMin(&g[FPG_CLAIM], p);
+            if (claimer && trep != FPS_INF) atomicMin(&tmin[trep], p);
+            if (elig) atomicMin(&g[FPG_EMIN], p);
+            if (srep != FPS_INF) atomicMin(&smin[srep], p);
+        }
+        __syncthreads();
+        if (g[FPG_ALL] == FPS_INF) break;  // (workgroup-uniform: an LDS word behind the barrier)
+        if (round > n) {                   // never: every round decides its lowest undecided packet
+            if (tid == 0)
+                __hip_atomic_fetch_add(&f.ctl[PPE_FCTL_ERR], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            break;
+        }
+        rounds = round + 1u;
+        const bool ready = und && (trep == FPS_INF || tmin[trep] >= p) && (srep == FPS_INF || smin[srep] == p) &&
+                           (!claimer || !ftight || g[FPG_CLAIM] == p) && (!elig || !rtight || g[FPG_EMIN] == p);
+        if (ready) {
+            und = false;
+            const uint32_t c = trep != FPS_INF ? created[trep] : FPS_INF;
+            if (c < p) {  // the flow was created earlier in this batch: found, never at the detector (flow.c:197-201)
+                outc = FPS_FOUND;
+                cidx = c;
+            } else if (elig) {  // PortScan_Detect (dp_portscan.c:231-272)
+                uint32_t res = PPE_PS_NOMEM;
+                if (srep != FPS_INF) {
+                    uint32_t w = s_ld[srep];
+                    if (!(w & (PPE_PS_LIVE | FPS_NOREC))) {  // the source's first call: pcb_create (:254-266)
+                        // (rtight: the candidates run one at a time, so the count is final; else records cannot run out)
+                        const bool grant = !rtight || g[FPG_GRANTED] < g[FPG_PSFREE];
+                        if (grant) atomicAdd(&g[FPG_GRANTED], 1u);
+                        w = grant ? (uint32_t)PPE_PS_LIVE : FPS_NOREC;
+                    }
+                    if (w & PPE_PS_LIVE) {
+                        PsState st;
+                        st.hold = s_hold[srep] | ((uint64_t)s_hold[BLOCK + srep] << 32);
+                        st.lc = s_lc[srep] | ((uint64_t)s_lc[BLOCK + srep] << 32);
+                        st.ld = w & 0xffffu;
+                        st.exc = s_exc[srep];
+                        st.lexc = s_lexc[srep];
+                        res = ps_step(st, r.z >> 16, ts, a.ps);
+                        s_hold[srep] = (uint32_t)st.hold;
+                        s_hold[BLOCK + srep] = (uint32_t)(st.hold >> 32);
+                        s_lc[srep] = (uint32_t)st.lc;
+                        s_lc[BLOCK + srep] = (uint32_t)(st.lc >> 32);
+                        s_exc[srep] = st.exc;
+                        s_lexc[srep] = st.lexc;
+                        w = st.ld | PPE_PS_LIVE | FPS_STEPPED;
+                    }
+                    s_ld[srep] = w;
+                }
+                atomicAdd(&g[FPG_CNT0 + res], 1u);
+                if (res != PPE_PS_OK && a.ps.action == 0u) {  // flow.c:216-230: before the ACL's verdict counts
+                    outc = FPS_PSDROP;
+                    atomicAdd(&g[FPG_CNT0 + 4u], 1u);
+                } else if (claimer && trep != FPS_INF) {  // FlowAdd (flow.c:120-158), or the pool is empty (:124-129)
+                    // (ftight: the claimers run one at a time; else the pool cannot run out in this batch)
+                    const bool room = !ftight || g[FPG_NCREATED] < g[FPG_ROOM];
+                    if (room) {
+                        atomicAdd(&g[FPG_NCREATED], 1u);
+                        created[trep] = p;
+                    }
+                    outc = room ? FPS_CREATE : FPS_NOMEM;
+                }
+            }
+        }
+        __syncthreads();
+    }
+    // ---- finalize ----
+    const uint64_t act_table = make_act_table<PPE_ST__END>(a.k.unsup_fw);
+    uint32_t act = (v >> 8) & 0xffu;
+    bool is_new = false, tomb = false;
+    if (pend) {
+        uint32_t st = prov, flags = v >> 16;
+        if (outc == FPS_FOUND) {
+            const uint4 rc = ((const uint4 *)f.rec)[cidx];
+            st = PPE_ST_ACL_FW;
+            flags = (flags & ~PPE_F_ACL) | flow_account(f, s, rc.x, rc.z, r.x, r.z, a.t.len[p], a.k.now);
+            if (a.t.hit) a.t.hit[p] = -1;
+        } else if (outc == FPS_CREATE) {  // FlowAdd oriented as this packet, then FlowUpdate
+            st = PPE_ST_ACL_FW;
+            is_new = true;
+            flags |= PPE_F_NEWFLOW | flow_account(f, s, r.x, r.z, r.x, r.z, a.t.len[p], a.k.now);
+            ((uint4 *)f.keys)[(size_t)(PPE_FLOW_SLOT_WORDS / 4u) * s] = make_uint4(r.x, r.y, r.z, PPE_FS_LIVE(r.w & 0xffu));
+        } else if (outc == FPS_NOMEM) {
+            st = PPE_ST_FLOW_NOMEM;
+        } else if (outc == FPS_PSDROP) {  // as the stateless PSC kernels emit it
+            st = PPE_ST_PORTSCAN_DROP;
+            flags &= ~(uint32_t)PPE_F_ACL;
+            if (a.t.hit) a.t.hit[p] = -1;
+        }
+        // a claimed slot that ends the batch without a creator: a tombstone, by the slot's lowest claimer
+        if (claimer && trep == p && created[p] == FPS_INF) {
+            f.keys[(size_t)PPE_FLOW_SLOT_WORDS * s + 3u] = PPE_FS_TOMB;
+            tomb = true;
+        }
+        act = (uint32_t)(act_table >> (2u * st)) & 3u;
+        a.t.verdict[p] = st | (act << 8) | (flags << 16);
+        atomicAdd(&bins[st | ((flags & 7u) << 5)], 1u);
+    }
+    if (mask != 0ull)  // (wave-uniform; a tile without pending packets was completed by the classify phase)
+        compact_tile(a.t.fw_idx, a.t.drop_idx, a.t.tile_cnt, n, 0u, wv, lane, valid, act, ~0u, a.t.part8);
+    const uint32_t ncr = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(is_new)),
+                   ntb = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(tomb));
+    if (lane == 0 && ncr) {
+        __hip_atomic_fetch_add(&f.ctl[PPE_FCTL_LIVE], (unsigned long long)ncr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add(&f.ctl[PPE_FCTL_NEW_FLOW], (unsigned long long)ncr, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (lane == 0 && ntb)
+        __hip_atomic_fetch_add(&f.ctl[PPE_FCTL_TOMBS], (unsigned long long)ntb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // the sources' records back (their owners): last_cycle, hold, the counts, the port; cycle = now for a source whose
+    // detector ran (find-or-create stamps it, also for HOLD); firstinv back to 0, also for a key without a record
+    if (pslot != PPE_PS_NOSLOT && srep == p) {
+        unsigned long long *rec = a.ps.recs + (size_t)pslot * PPE_PS_REC_WORDS;
+        const uint32_t w = s_ld[p];
+        if (w & PPE_PS_LIVE) {
+            PsState st;
+            st.hold = s_hold[p] | ((uint64_t)s_hold[BLOCK + p] << 32);
+            st.lc = s_lc[p] | ((uint64_t)s_lc[BLOCK + p] << 32);
+            st.ld = w & 0xffffu;
+            st.exc = s_exc[p];
+            st.lexc = s_lexc[p];
+            ps_store(rec, st, PPE_PS_LIVE);
+            if (w & FPS_STEPPED) rec[1] = a.ps.now_cycles;
+        } else {
+            rec[4] = 0ull;
+        }
+    }
+    __syncthreads();
+    for (uint32_t b = tid; b < PPE_NBINS; b += BLOCK) {
+        const uint32_t c = bins[b];
+        if (c)
+            for (uint32_t cb = bin_counters<true>(b, act_table); cb; cb &= cb - 1u) atomicAdd(&lcnt[__builtin_ctz(cb)], c);
+    }
+    __syncthreads();
+    if (tid < PPE_C__COUNT && lcnt[tid])
+        __hip_atomic_fetch_add(&a.k.cslots[tid], (unsigned long long)lcnt[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // the detector's counts: the four results and the drops, the keys and records taken (new_pcb with the live count)
+    if (tid >= 64u && tid < 64u + 8u) {
+        const uint32_t k = tid - 64u;
+        const uint32_t idx[8] = {PPE_PSC_OK, PPE_PSC_NOMEM, PPE_PSC_DETECTED, PPE_PSC_HOLD,
+                                 PPE_PSC_DROP, PPE_PSC_OCC, PPE_PSC_LIVE, PPE_PSC_NEW};
+        const uint32_t c = k < 5u ? g[FPG_CNT0 + k] : k == 5u ? g[FPG_OCC] : g[FPG_GRANTED];
+        if (c) __hip_atomic_fetch_add(&a.ps.ctl[idx[k]], (unsigned long long)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (tid == 128u)
+        __hip_atomic_store(&f.ctl[PPE_FCTL_PS_ROUNDS], (unsigned long long)rounds, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+#endif
+
 // FlowTimeOut + FlowAgeTimeoutCB (flow.c:391-467): live flows idle for more than `timeout` become tombstones.
 template <int BLOCK>
 __global__ __launch_bounds__(BLOCK) void ppe_flow_age_kernel(ppe_flow_kargs a) {
@@ -2815,6 +3120,29 @@ extern "C" int ppe_launch_flow_small(const ppe_kargs *a, const ppe_flow_small_ta
     if (mode == IMG_LDS) hipExtLaunchKernelGGL(ppe_flow_small_kernel<IMG_LDS>, g, b, shmem, s, e0, e1, 0, k);
     else if (mode == IMG_SPLIT) hipExtLaunchKernelGGL(ppe_flow_small_kernel<IMG_SPLIT>, g, b, shmem, s, e0, e1, 0, k);
     else hipExtLaunchKernelGGL(ppe_flow_small_kernel<IMG_GLOBAL>, g, b, shmem, s, e0, e1, 0, k);
+    return (int)hipGetLastError();
+}
+#elif defined(PPE_TU_FLOW_PS)
+// csrc/ppe_kernels_flow_portscan.hip: this file again, exporting only the one-launch flow kernel with the port-scan
+// detector inside over the three image placements of the flow-table plan, at 1024 threads
+extern "C" int ppe_launch_flow_portscan(const ppe_kargs *a, const ppe_flow_small_tail *t, const ppe_ps_kargs *ps, int mode,
+                                        void *stream, void *ev_start, void *ev_stop) {
+    const hipStream_t s = (hipStream_t)stream;
+    const hipEvent_t e0 = (hipEvent_t)ev_start, e1 = (hipEvent_t)ev_stop;
+    if (a->flow.upd_wgs != 0u || a->nbatch != 1u || a->ring || a->batch[0].n == 0u || a->batch[0].n > PPE_FLOW_PS_MAX)
+        return (int)hipErrorInvalidValue;
+    ppe_flow_ps_kargs k;
+    k.k = *a;
+    k.t = *t;
+    k.ps = *ps;
+    // the classify kernel's LDS at this block size (key slots, bins, bucket cursors, the staged image); the resolve and
+    // finalize phases live in the part in front of the image
+    const size_t base = ppe_classify_fixed_lds(PPE_FLOW_PS_BLOCK, PF_HOIST, mode) + ppe_flow_lds_extra();
+    const size_t shmem = mode == IMG_GLOBAL ? base : base + (((size_t)a->stage_words * 4u + 1023u) & ~(size_t)1023u);
+    const dim3 g(1), b(PPE_FLOW_PS_BLOCK);
+    if (mode == IMG_LDS) hipExtLaunchKernelGGL(ppe_flow_ps_kernel<IMG_LDS>, g, b, shmem, s, e0, e1, 0, k);
+    else if (mode == IMG_SPLIT) hipExtLaunchKernelGGL(ppe_flow_ps_kernel<IMG_SPLIT>, g, b, shmem, s, e0, e1, 0, k);
+    else hipExtLaunchKernelGGL(ppe_flow_ps_kernel<IMG_GLOBAL>, g, b, shmem, s, e0, e1, 0, k);
     return (int)hipGetLastError();
 }
 #elif defined(PPE_TU_STREAM)

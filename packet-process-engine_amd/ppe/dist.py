@@ -121,6 +121,10 @@ class DeviceSteerOps:
         """Attack monitors are attached to this engine (Engine.attack; ppe_classify_flow then returns PPE_ENOTSUP)."""
         return getattr(self.eng, "attack_attached", None) is not None
 
+    def portscan_flow_attached(self) -> bool:
+        """A port-scan table is attached to this engine's flow-table path (PortScan.attach_flow)."""
+        return getattr(self.eng, "portscan_flow_attached", None) is not None
+
     def attack_flow_attached(self) -> bool:
         """Attack monitors are attached to this engine's flow-table path (Attack.attach_flow): the steered path, which
         would split the per-port state over the ranks, refuses them."""
@@ -170,6 +174,11 @@ def steered_classify_flow(ops, dist, hdr, lens, cfg, world: int, rank: int) -> d
     if getattr(ops, "attack_flow_attached", None) and ops.attack_flow_attached():
         raise PPEError(f"steered ppe_classify_flow failed: {abi.PPE_ENOTSUP}: attack monitors are attached to the "
                        "flow-table path (ppe_flow_attack_attach); the steered path does not support them")
+    # a port-scan table on the flow-table path: a source's detector chain would span ranks (its packets are steered by
+    # flow, not by source), which is not the reference's one record per source
+    if getattr(ops, "portscan_flow_attached", None) and ops.portscan_flow_attached():
+        raise PPEError(f"steered ppe_classify_flow failed: {abi.PPE_ENOTSUP}: a port-scan table is attached to the "
+                       "flow-table path (ppe_flow_portscan_attach); the steered path does not support it")
     perm, counts, send_hdr, send_len = steer_prepare(ops, hdr, lens, cfg, world, rank)
     send_counts = counts.to(torch.int64)
     recv_counts = torch.empty_like(send_counts)

@@ -199,11 +199,21 @@ class Engine:
         return res
 
     def flow_launch_info(self) -> tuple:
-        """ppe_flow_launch_info: (kind, launches) of the last flow batch: (1, 1) the one-launch kernel, (0, 2) the two
-        launches, (0, 0) before the first."""
+        """ppe_flow_launch_info: (kind, launches) of the last flow batch: (1, 1) the one-launch kernel, (2, 1) the
+        one-launch kernel with the port-scan detector inside, (0, 2) the two launches, (0, 0) before the first."""
         k, n = C.c_uint32(9), C.c_uint32(9)
         self._check(self.lib.ppe_flow_launch_info(self.ctx, C.byref(k), C.byref(n)), "ppe_flow_launch_info")
         return k.value, n.value
+
+    def flow_portscan_max(self) -> int:
+        """ppe_flow_portscan_max: the packets one device flow batch takes with a port-scan table flow-attached."""
+        return int(self.lib.ppe_flow_portscan_max())
+
+    def flow_portscan_rounds(self) -> int:
+        """ppe_flow_portscan_rounds: resolve rounds of the last flow batch with the detector inside (debug count)."""
+        r = C.c_uint32(0)
+        self._check(self.lib.ppe_flow_portscan_rounds(self.ctx, C.byref(r)), "ppe_flow_portscan_rounds")
+        return r.value
 
     def flow_age(self, now: int, timeout: int = 20) -> int:
         d = C.c_uint64(0)
@@ -273,9 +283,13 @@ class Engine:
     # ---- port-scan detector (ppe_portscan_*, dataplane/src/attack/dp_portscan.c) ----
     def portscan(self, attach: bool = True, **cfg) -> "PortScan":
         """ppe_portscan_create (cfg: the words of ppe_portscan_cfg_t; none given = the reference's defaults) and, unless
-        attach is false, ppe_portscan_attach: later ppe_classify / ppe_classify_batches launches run the detector."""
+        attach is false, ppe_portscan_attach: later ppe_classify / ppe_classify_batches launches run the detector.
+        attach="flow": ppe_flow_portscan_attach instead: later ppe_classify_flow calls run it on flow misses; the
+        stateless calls then run without it."""
         ps = PortScan(self, **cfg)
-        if attach:
+        if attach == "flow":
+            ps.attach_flow()
+        elif attach:
             ps.attach()
         return ps
 
@@ -428,11 +442,23 @@ class PortScan:
         self.eng._check(self.lib.ppe_portscan_attach(self.eng.ctx, None), "ppe_portscan_attach")
         self.eng.portscan_attached = None
 
+    def attach_flow(self):
+        """ppe_flow_portscan_attach: ppe_classify_flow / _flow_host run the detector on flow misses (batches of at most
+        Engine.flow_portscan_max() packets on the device); the engine's stateless calls do not see the table."""
+        self.eng._check(self.lib.ppe_flow_portscan_attach(self.eng.ctx, self.h), "ppe_flow_portscan_attach")
+        self.eng.portscan_flow_attached = self
+
+    def detach_flow(self):
+        self.eng._check(self.lib.ppe_flow_portscan_attach(self.eng.ctx, None), "ppe_flow_portscan_attach")
+        self.eng.portscan_flow_attached = None
+
     def close(self):
         if self.h:
-            self.lib.ppe_portscan_destroy(self.h)  # (detaches it first)
+            self.lib.ppe_portscan_destroy(self.h)  # (detaches it first, from whichever point holds it)
             if getattr(self.eng, "portscan_attached", None) is self:
                 self.eng.portscan_attached = None
+            if getattr(self.eng, "portscan_flow_attached", None) is self:
+                self.eng.portscan_flow_attached = None
             self.h = C.c_void_p()
 
     def clock(self, now_cycles: int, now_seconds: int):
