@@ -44,13 +44,22 @@ def tcp_packet(sip=0xC0A80101, dip=0xC0A80102, sport=12345, dport=443, flags=0x0
     return (eth(0x8100) + vlan(0x0800) if vlan_tag else eth(0x0800)) + l3
 
 
-def ip_frag(proto, sip, dip, ip_id, off_bytes, mf, chunk, ihl=5, vlan_tag=False, pad=0):
-    """One IPv4 fragment frame: fragment offset off_bytes (a multiple of 8), MF flag, payload chunk."""
+def ip_frag(proto, sip, dip, ip_id, off_bytes, mf, chunk, ihl=5, vlan_tag=False, pad=0, *, etype=None, inner=0x0800,
+            ver=4, ip_len=None, offw=None, dmac=DMAC, smac=SMAC):
+    """One IPv4 fragment frame: fragment offset off_bytes (a multiple of 8), MF flag, payload chunk.  The keyword
+    arguments set what an edge case needs and nothing else can: etype = the outer ethertype (default 0x8100 with
+    vlan_tag, else 0x0800), inner = the type behind a tag, ver, ip_len, offw = the raw ip_off word, the MACs."""
     hlen = ihl * 4
-    offw = (off_bytes >> 3) | (0x2000 if mf else 0)
-    h = struct.pack(">BBHHHBBHII", 0x40 | ihl, 0, hlen + len(chunk), ip_id, offw, 64, proto, 0, sip, dip)
+    if offw is None:
+        offw = (off_bytes >> 3) | (0x2000 if mf else 0)
+    if ip_len is None:
+        ip_len = hlen + len(chunk)
+    h = struct.pack(">BBHHHBBHII", (ver << 4) | ihl, 0, ip_len, ip_id, offw, 64, proto, 0, sip, dip)
     h += b"\x01" * (hlen - 20)
-    l2 = eth(0x8100) + vlan(0x0800) if vlan_tag else eth(0x0800)
+    if vlan_tag:
+        l2 = eth(0x8100 if etype is None else etype, dmac, smac) + vlan(inner)
+    else:
+        l2 = eth(0x0800 if etype is None else etype, dmac, smac)
     return l2 + h + chunk + b"\0" * pad
 
 
