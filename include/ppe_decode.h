@@ -35,6 +35,7 @@ extern "C" {
 
 /* mbuf flags (dataplane/src/decode/decode.h:12-21) */
 #define PKT_IP_FRAG    (1 << 1)
+#define PKT_FRAG_REASM_COMP (1 << 3)   /* a reassembled datagram's mbuf (decode.h:14, decode-defrag.c:274) */
 #define PKT_TO_SERVER  (1 << 4)
 #define PKT_TO_CLIENT  (1 << 5)
 #define PKT_HAS_FLOW   (1 << 8)
@@ -199,6 +200,48 @@ void DP_Flow_Clock(uint64_t now_seconds);
 /* FlowAgeTimeoutCB (flow.c:391-467) at now_seconds with FLOW_MAX_TIMEOUT = 20: flows idle for more than 20 s are
  * deleted; *deleted (may be NULL) = their number.  PPE_OK with 0 deleted without a table. */
 int  DP_Flow_Age(uint64_t now_seconds, uint64_t *deleted);
+
+/* Defrag behind Decode (decode-ipv4.c:102-125: no fragment leaves DecodeIPV4 unhandled), read per flush.  Start values:
+ * defrag_able 0 (OFF: Decode hands every fragment to the punt hook; the reference has no such switch, it is always
+ * on), defrag_cache_max 8 (decode-defrag.c:24), read when the table is created.  With defrag_able == 1 a flush
+ *   - classifies the burst as without it, on whichever path the other switches select;
+ *   - runs its fragments (status PPE_ST_FRAG) through ppe_defrag_host (ppe_hip.h) in burst order, whole frames
+ *     gathered from pkt_ptr / pkt_totallen, now_seconds = DP_Defrag_Clock's; the first such flush creates the table
+ *     (DEFRAG_FCB_MAX = 1,024 FCBs of defrag_cache_max fragments);
+ *   - holds a cached fragment (PPE_DF_CACHED, and PPE_DF_SETUP_ERR): no hook is called for it
+ *     (decode-defrag.c:391-392, 281-283).  The caller keeps the mbuf object alive until a hook gets it; pkt_ptr is
+ *     not read again (the device store holds the copy, as PACKET_HW2SW's);
+ *   - hands a fragment Defrag drops (FCB_FULL, HW2SW_ERR, DELETED, CACHE_FULL, DEFRAG_ERR) to the drop hook, with
+ *     DP_Log_Func only where decode-defrag.c calls it (:436, cache full; here before the drop hook, as for every
+ *     logged drop, so the hook may free the mbuf);
+ *   - builds, for a fragment that completes its datagram, the reassembled mbuf as Frag_defrag_setup / _reasm leave it
+ *     (:164-220, 241-276): zeroed, PKTBUF_SW, MBUF_MAGIC_NUM, input_port of the chain's head, timestamp 0, pkt_ptr the
+ *     reassembled frame, pkt_totallen its length, flags PKT_FRAG_REASM_COMP, fragments = the caller's mbufs in chain
+ *     order linked through next.  The burst's datagrams are classified from their frames like any other mbuf, as a
+ *     second burst behind the first in the order of their completing fragments, on the same path.  At burst 1 that is
+ *     the reference's order (Defrag's datagram goes on into DecodeTCP / DecodeUDP / the flow table before the next
+ *     packet); at a larger burst a datagram counts as arriving behind its burst's last packet;
+ *   - calls the hooks in burst order with no lock held: the datagram's one call (fw, drop with DP_Log_Func as for
+ *     any packet, or punt) takes the place of its completing fragment.  The reassembled mbuf and its frame are the
+ *     shim's and valid during the call; the chain belongs to the hook (output.c:122-170 forwards or frees it).
+ * Decode_Flush then returns the number of hook calls.  Setting defrag_able back to 0 keeps the table and what it
+ * holds (DP_Defrag_Age still works).  When the defrag step or the datagrams' classify step fails, every undelivered
+ * mbuf of the burst goes to the drop hook and so does everything the table held; the table is destroyed and created
+ * afresh at the next flush.  Not built: per-fragment monitor counting, teardrop as an action, zero-copy for pinned
+ * frames. */
+extern uint32_t defrag_able;
+extern uint32_t defrag_cache_max;
+/* FCB_UPDATE_TIMESTAMP's clock (seconds) for the bursts flushed afterwards, by value.  Starts at 0. */
+void DP_Defrag_Clock(uint64_t now_seconds);
+/* Frag_defrag_timeout (decode-defrag.c:490-551) at now_seconds with FRAG_MAX_TIMEOUT = 20: completed FCBs and those
+ * idle for more than 20 s are freed; every fragment they held goes to the drop hook (no DP_Log_Func); *dropped (may
+ * be NULL) = their number.  PPE_OK with 0 dropped without a table. */
+int  DP_Defrag_Age(uint64_t now_seconds, uint64_t *dropped);
+/* the FCB table for ppe_defrag_info / ppe_format_pkt_stat_ex / ppe_format_flow_stat_ex (ppe_hip.h); NULL before the
+ * first flush with defrag_able == 1 that carries a fragment and after DP_Acl_Rule_Release (which hands every held
+ * mbuf to the drop hook first) */
+struct ppe_defrag_table;
+struct ppe_defrag_table *DP_Defrag_Table(void);
 
 void Decode(mbuf_t *m);
 /* Classify every mbuf the calling thread has queued; returns the number delivered through the output hooks, or a

@@ -569,6 +569,25 @@ int  ppe_defrag(ppe_defrag_t *d, const ppe_frag_batch_t *in, const ppe_defrag_ou
 int  ppe_defrag_age(ppe_defrag_t *d, uint64_t now_seconds, uint64_t timeout_seconds, uint64_t *dropped,
                     uint32_t max, uint32_t *n_dropped, uint32_t *n_freed);
 int  ppe_defrag_info(ppe_defrag_t *d, ppe_defrag_info_t *info);      /* synchronises */
+/* How the last ppe_defrag batch of d ran, without synchronising: *kind 1 and *launches 1 for the one-launch kernel (a
+ * batch of at most 4 fragments, the measured cutoff, runs its six phases in one workgroup; byte-identical outputs and
+ * table state, and both shapes interleave freely on one table), *kind 0 and *launches 6 otherwise: a larger batch, a
+ * table created with PPE_DEFRAG_SMALL=0 in the environment (the A/B switch), or the PPE_DF_LOOK_FAIL test hook armed.
+ * (0, 0) before the first batch.  Diagnostic: PPE_DEFRAG_SMALL=N with N > 1 at ppe_defrag_create gives that table the
+ * one launch up to min(N, 256) fragments, the kernel's workgroup, instead of the cutoff (for measuring and testing the
+ * kernel past it: slower than six launches from 8 fragments on); unset or 1: the cutoff. */
+int  ppe_defrag_launch_info(ppe_defrag_t *d, uint32_t *kind, uint32_t *launches);
+/* ppe_defrag for a batch in host memory: every pointer of in and out is a host pointer (pageable or pinned), and
+ * out->n_dgram is an optional host word.  The batch runs as consecutive ppe_defrag batches of `chunk` fragments
+ * (0, or more than max_batch: max_batch) on one ordered stream of the table's own; datagram indices run on across
+ * the chunks, and every output and ppe_defrag_info is the same whatever the chunk (ppe_defrag is one core's run in
+ * index order and now_seconds is constant over the call).  Only status, dgram_of (n entries each) and the rows of the
+ * datagrams that exist (dgram_len / dgram_hdr / dgram_pkt / dgram_frags rows below the count) are written.  in->id
+ * NULL: the index in the whole batch.  Synchronises before it returns.  PPE_EINVAL for a missing required pointer or
+ * a wrong hdr_stride, and PPE_EIO for a look-back error pending when the call begins: nothing is written on either.
+ * A device error or a look-back error that a chunk of this call raises also returns PPE_EIO, with the outputs of the
+ * chunks before it written. */
+int  ppe_defrag_host(ppe_defrag_t *d, const ppe_frag_batch_t *in, const ppe_defrag_out_t *out, uint32_t chunk);
 
 /* ---- Port-scan detector on the stateless classify path (dataplane/src/attack/dp_portscan.c) ----
  * The reference runs PortScan_Detect on every flow miss after syn_check and before the ACL (flow.c:215-230).  The

@@ -335,6 +335,28 @@ uint32_t ppe_pick_flow_small(uint32_t n, int small_allowed, int atk_flow_attache
     return (n >= 1u && n <= PPE_FLOW_SMALL_CUTOFF && small_allowed && !atk_flow_attached) ? 1u : 0u;
 }
 
+// one launch of one workgroup for a small fragment batch (csrc/ppe_defrag_small.hip): up to `upto` fragments (the
+// table's: the measured cutoff, 0 under PPE_DEFRAG_SMALL=0, the diagnostic PPE_DEFRAG_SMALL=N's value; never past the
+// workgroup), unless the look-back failure hook is armed (one workgroup has no look-back to fail).  The one decision
+// point: ppe_defrag calls this form with its table's value.
+uint32_t ppe_pick_defrag_small_upto(uint32_t n, uint32_t upto, int look_fail_armed) {
+    if (upto > (uint32_t)PPE_DEFRAG_SMALL_BLOCK) upto = (uint32_t)PPE_DEFRAG_SMALL_BLOCK;
+    return (n >= 1u && n <= upto && !look_fail_armed) ? 1u : 0u;
+}
+
+// the same for a table at its default: up to the measured cutoff when the table allows it
+uint32_t ppe_pick_defrag_small(uint32_t n, int small_allowed, int look_fail_armed) {
+    return ppe_pick_defrag_small_upto(n, small_allowed ? PPE_DEFRAG_SMALL_CUTOFF : 0u, look_fail_armed);
+}
+
+// what PPE_DEFRAG_SMALL (its integer value, or -1 when unset) makes of a new table's `upto`: unset or 1 the cutoff, 0
+// none (the A/B switch), N > 1 min(N, the workgroup) (diagnostic)
+uint32_t ppe_defrag_small_upto_from_env(int value) {
+    if (value == 0) return 0u;
+    if (value < 0 || value == 1) return PPE_DEFRAG_SMALL_CUTOFF;
+    return (uint32_t)value < (uint32_t)PPE_DEFRAG_SMALL_BLOCK ? (uint32_t)value : (uint32_t)PPE_DEFRAG_SMALL_BLOCK;
+}
+
 // the port-scan detector on the flow-table path (csrc/ppe_kernels_flow_portscan.hip): with a table flow-attached and its
 // detector on, a batch of up to one workgroup's worth of packets takes the kernel with the detector inside; a larger one
 // is refused (whether a packet reaches the detector depends on verdicts of earlier packets of the batch: a grid-wide form

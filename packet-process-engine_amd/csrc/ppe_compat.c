@@ -46,6 +46,11 @@ uint32_t flow_able = 0;
 /* PortScan_Detect on the flow table's misses (flow.c:215-230): off until set, with flow_able == 1 only (ppe_decode.h) */
 uint32_t flow_portscan_able = 0;
 uint32_t flow_item_num = 100000;
+/* Defrag behind Decode (decode-ipv4.c:102-125, decode-defrag.c:449-487), read per flush.  The reference has no such
+ * switch (DecodeIPV4 always hands a fragment to Defrag); this library starts with it OFF, like the ones above: Decode
+ * punts fragments.  defrag_cache_max: decode-defrag.c:24, read when the table is created. */
+uint32_t defrag_able = 0;
+uint32_t defrag_cache_max = 8;
 PluginModule plugin_modules[PLUGIN_SIZE];
 
 struct ppe_tree_set {
@@ -77,6 +82,16 @@ static uint64_t g_ps_cycles = 0, g_ps_seconds = 0;
  * and the clock DP_Flow_Clock last gave; both under g_ctx_lock */
 static int g_flow = 0;
 static uint64_t g_flow_now = 0;
+/* the FCB table (created by the first flush with defrag_able == 1 that has a fragment, destroyed with the context),
+ * the clock DP_Defrag_Clock last gave, and the registry of the mbufs the table holds: a fragment's id in the table is
+ * its slot here (never ~0), free slots on a stack; all under g_ctx_lock */
+static ppe_defrag_t *g_df = NULL;
+static uint64_t g_df_now = 0;
+/* of the table: fcb_max x cache_max (the most fragments it holds), cache_max, fcb_max, reasm_buf_bytes */
+static uint32_t g_df_ids = 0, g_df_cm = 0, g_df_fcb = 0, g_df_rb = 0;
+static mbuf_t **g_held = NULL;
+static uint32_t *g_held_free = NULL;
+static uint32_t g_held_cap = 0, g_held_nfree = 0;
 static fw_alert fw_log_fun = NULL;
 static ppe_output_fn out_fw = NULL, out_drop = NULL, out_punt = NULL;
 
@@ -92,6 +107,53 @@ void ppe_set_output_hooks(ppe_output_fn fw, ppe_output_fn drop, ppe_output_fn pu
     out_fw = fw;
     out_drop = drop;
     out_punt = punt;
+}
+
+/* ---- the registry of held fragments (caller holds g_ctx_lock) ---- */
+static uint64_t held_put(mbuf_t *m) {  /* the mbuf's handle, or ~0 without memory */
+    if (!g_held_nfree) {
+        const uint32_t cap = g_held_cap ? g_held_cap * 2u : 1024u;
+        mbuf_t **h = (mbuf_t **)realloc(g_held, sizeof(*h) * cap);
+        if (h) g_held = h;
+        uint32_t *f = h ? (uint32_t *)realloc(g_held_free, sizeof(*f) * cap) : NULL;
+        if (f) g_held_free = f;
+        if (!h || !f) return ~0ull;
+        for (uint32_t k = cap; k > g_held_cap; k--) {  /* (the lowest new slot on top) */
+            g_held[k - 1] = NULL;
+            g_held_free[g_held_nfree++] = k - 1;
+        }
+        g_held_cap = cap;
+    }
+    const uint32_t s = g_held_free[--g_held_nfree];
+    g_held[s] = m;
+    return s;
+}
+
+static mbuf_t *held_take(uint64_t h) {  /* the mbuf behind a handle (NULL: not one of ours), its slot free again */
+    if (h >= g_held_cap || !g_held[h]) return NULL;
+    mbuf_t *m = g_held[h];
+    g_held[h] = NULL;
+    g_held_free[g_held_nfree++] = (uint32_t)h;
+    return m;
+}
+
+/* Destroy the FCB table and empty the registry: returns the mbufs it held (malloc'd array, *n entries; NULL when
+ * none, or without memory for the list: then they are lost to the hooks, as a reference core that runs out of memory
+ * loses them) for the caller to hand to the drop hook once no lock is held. */
+static mbuf_t **defrag_reset_locked(uint32_t *n) {
+    *n = 0;
+    if (g_df) ppe_defrag_destroy(g_df);
+    g_df = NULL;
+    uint32_t live = g_held_cap - g_held_nfree;
+    mbuf_t **out = live ? (mbuf_t **)malloc(sizeof(*out) * live) : NULL;
+    for (uint32_t s = 0; s < g_held_cap; s++)
+        if (g_held[s] && out) out[(*n)++] = g_held[s];
+    free(g_held);
+    free(g_held_free);
+    g_held = NULL;
+    g_held_free = NULL;
+    g_held_cap = g_held_nfree = 0;
+    return out;
 }
 
 int DP_Acl_Rule_Init(void) {
@@ -189,6 +251,8 @@ void DP_Acl_Rule_Release(void) {
     pthread_mutex_lock(&g_ctx_lock);  /* no flush, commit or lookup is using the context being destroyed */
     if (g_ps) ppe_portscan_destroy(g_ps);  /* (before its context) */
     g_ps = NULL;
+    uint32_t nheld = 0;
+    mbuf_t **held = defrag_reset_locked(&nheld);  /* the FCB table, and what it held for the drop hook below */
     if (g_ctx) ppe_ctx_destroy(g_ctx);  /* (its flow table with it) */
     g_ctx = NULL;
     g_flow = 0;
@@ -200,6 +264,9 @@ void DP_Acl_Rule_Release(void) {
     DP_Acl_Rule_Clean(&g_acltree_1.TreeSet, &g_acltree_1.TreeNode);
     DP_Acl_Rule_Clean(&g_acltree_2.TreeSet, &g_acltree_2.TreeNode);
     pthread_mutex_unlock(&g_lock);
+    for (uint32_t i = 0; i < nheld; i++)  /* (no lock held) */
+        if (out_drop) out_drop(held[i]);
+    free(held);
 }
 
 int DP_Acl_Rule_Commit(void) {
@@ -313,6 +380,15 @@ static int take_fail(void) {
     while (k)
         if (__atomic_compare_exchange_n(&g_fail_alloc, &k, k - 1, 0, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) return 1;
     return 0;
+}
+/* Test hook (tests/test_gpu_compat_defrag.py only, not in the public headers): the next flush with defrag_able == 1
+ * that reaches step `step` fails there with PPE_EIO, once: 1 the defrag step (before ppe_defrag_host, its mbufs already
+ * in the registry), 2 the datagrams' classify step.  0 disarms. */
+static volatile uint32_t g_fail_step = 0;
+void ppe_compat_debug_fail_defrag_step(uint32_t step) { __atomic_store_n(&g_fail_step, step, __ATOMIC_RELAXED); }
+static int take_step_fail(uint32_t step) {
+    uint32_t want = step;
+    return __atomic_compare_exchange_n(&g_fail_step, &want, 0u, 0, __ATOMIC_RELAXED, __ATOMIC_RELAXED);
 }
 static void *burst_alloc(size_t bytes, size_t align) {
     if (take_fail()) return NULL;
@@ -572,6 +648,244 @@ static int classify_mbufs(mbuf_t **mb, uint32_t n) {
     return rc;
 }
 
+/* ---- Defrag behind Decode (decode-ipv4.c:102-125; ppe_decode.h) ---- */
+void DP_Defrag_Clock(uint64_t now_seconds) {
+    pthread_mutex_lock(&g_ctx_lock);
+    g_df_now = now_seconds;
+    pthread_mutex_unlock(&g_ctx_lock);
+}
+
+ppe_defrag_t *DP_Defrag_Table(void) {
+    pthread_mutex_lock(&g_ctx_lock);
+    ppe_defrag_t *t = g_df;
+    pthread_mutex_unlock(&g_ctx_lock);
+    return t;
+}
+
+int DP_Defrag_Age(uint64_t now_seconds, uint64_t *dropped) {
+    if (dropped) *dropped = 0;
+    pthread_mutex_lock(&g_ctx_lock);
+    if (!g_df) {
+        pthread_mutex_unlock(&g_ctx_lock);
+        return PPE_OK;
+    }
+    const uint32_t cap = g_df_ids ? g_df_ids : 1u;
+    uint64_t *ids = (uint64_t *)malloc(sizeof(*ids) * cap);
+    mbuf_t **mb = (mbuf_t **)malloc(sizeof(*mb) * cap);
+    uint32_t nd = 0, k = 0;
+    int rc = (ids && mb) ? ppe_defrag_age(g_df, now_seconds, 20u /* FRAG_MAX_TIMEOUT */, ids, g_df_ids, &nd, NULL)
+                         : PPE_ENOMEM;
+    if (rc == PPE_OK)
+        for (uint32_t i = 0; i < nd && i < g_df_ids; i++) {
+            mbuf_t *m = held_take(ids[i]);
+            if (m) mb[k++] = m;
+        }
+    pthread_mutex_unlock(&g_ctx_lock);
+    for (uint32_t i = 0; i < k; i++)  /* Frag_defrag_timeout: output_drop_proc per held fragment, no log (:538-544) */
+        if (out_drop) out_drop(mb[i]);
+    if (dropped) *dropped = k;
+    free(ids);
+    free(mb);
+    return rc;
+}
+
+/* what a flush with defrag_able == 1 does with mbuf i of the burst */
+enum { DF_BY_VERDICT = 0, DF_HELD, DF_DROP, DF_DROP_LOG, DF_DGRAM,
+       DF_CHAIN /* (after a failed step) on a chain this burst completed: dropped with the burst */,
+       DF_GONE /* (after a failed step) delivered elsewhere meanwhile */ };
+typedef struct {
+    uint8_t *disp;      /* n: DF_* */
+    uint32_t *dgram;    /* n: the datagram index of a DF_DGRAM mbuf */
+    mbuf_t *rm;         /* nd reassembled mbufs, classified */
+    uint8_t *frames;    /* their frames (rm[j].pkt_ptr points into it) */
+    uint32_t nd;
+    mbuf_t **lost;      /* after a failure: what the table held besides this burst's mbufs, for the drop hook */
+    uint32_t nlost;
+} df_step_t;
+
+static void df_step_free(df_step_t *d) {
+    free(d->disp);
+    free(d->dgram);
+    free(d->rm);
+    free(d->frames);
+    free(d->lost);
+}
+
+/* The fragments of a classified burst (status PPE_ST_FRAG) through the FCB table in burst order, then the datagrams
+ * they complete through the classify step as a second burst.  PPE_OK with d filled (d->disp NULL: the burst has no
+ * fragment), or a PPE_E* code: then the table is gone and d->lost holds what it held. */
+static int defrag_mbufs(mbuf_t **mb, uint32_t n, df_step_t *d) {
+    uint32_t nf = 0;
+    size_t bytes = 0;
+    for (uint32_t i = 0; i < n; i++)
+        if (PPE_VERDICT_STATUS(mb[i]->ppe_verdict) == PPE_ST_FRAG && mb[i]->pkt_ptr) {
+            nf++;
+            bytes += ((size_t)(mb[i]->pkt_totallen < 4096u ? mb[i]->pkt_totallen : 4096u) + 3u) & ~(size_t)3;
+        }
+    if (!nf) return PPE_OK;
+    const uint32_t ws = 128u;
+    d->disp = (uint8_t *)burst_alloc(n, 0);
+    d->dgram = (uint32_t *)burst_alloc((size_t)n * 4, 0);
+    uint32_t *at = (uint32_t *)burst_alloc((size_t)nf * 4, 0);          /* fragment k's index in the burst */
+    uint8_t *pkt = (uint8_t *)burst_alloc(bytes + 64, 0);
+    uint64_t *off = (uint64_t *)burst_alloc((size_t)nf * 8, 0), *id = (uint64_t *)burst_alloc((size_t)nf * 8, 0);
+    uint32_t *len = (uint32_t *)burst_alloc((size_t)nf * 4, 0), *st = (uint32_t *)burst_alloc((size_t)nf * 4, 0);
+    uint32_t *of = (uint32_t *)burst_alloc((size_t)nf * 4, 0), *dlen = (uint32_t *)burst_alloc((size_t)nf * 4, 0);
+    uint8_t *win = (uint8_t *)burst_alloc((size_t)nf * ws, 0);
+    uint64_t *chain = NULL;
+    mbuf_t **rmp = NULL;
+    uint32_t cm = 0, rb = 0, nd = 0, put = 0;
+    int rc = PPE_ENOMEM;
+    pthread_mutex_lock(&g_ctx_lock);
+    if (d->disp && d->dgram && at && pkt && off && id && len && st && of && dlen && win) {
+        rc = g_ctx ? PPE_OK : PPE_ENODEV;
+        if (rc == PPE_OK && !g_df) {  /* FragModule_init on first use: DEFRAG_FCB_MAX FCBs, defrag_cache_max fragments each */
+            ppe_defrag_cfg_t c = {1024u, defrag_cache_max, 0u, 0u, ((n > 4096u ? n : 4096u) + 63u) & ~63u, 0u};
+            rc = ppe_defrag_create(g_ctx, &c, &g_df);
+            if (rc != PPE_OK) g_df = NULL;
+            ppe_defrag_info_t fi;
+            if (rc == PPE_OK) rc = ppe_defrag_info(g_df, &fi);
+            if (rc == PPE_OK) {
+                g_df_ids = fi.fcb_max * fi.cache_max;
+                g_df_cm = fi.cache_max;
+                g_df_fcb = fi.fcb_max;
+                g_df_rb = fi.reasm_buf_bytes;
+            }
+        }
+        if (rc == PPE_OK) {
+            cm = g_df_cm;  /* (of the table, whatever the global says now) */
+            rb = g_df_rb;  /* ppe_defrag_host writes datagram j's frame at j x the table's reasm_buf_bytes */
+            chain = (uint64_t *)burst_alloc((size_t)nf * cm * 8, 0);
+            /* a call completes at most one datagram per fragment and per FCB record (none is freed inside a call) */
+            d->frames = (uint8_t *)burst_alloc((size_t)(nf < g_df_fcb ? nf : g_df_fcb) * rb, 0);
+            if (!chain || !d->frames) rc = PPE_ENOMEM;
+        }
+        size_t o = 0;
+        for (uint32_t i = 0, k = 0; rc == PPE_OK && i < n; i++) {
+            mbuf_t *m = mb[i];
+            d->disp[i] = DF_BY_VERDICT;
+            if (PPE_VERDICT_STATUS(m->ppe_verdict) != PPE_ST_FRAG || !m->pkt_ptr) continue;
+            const uint32_t c = m->pkt_totallen < 4096u ? m->pkt_totallen : 4096u;  /* (frag_buf_bytes <= 4096) */
+            memcpy(pkt + o, m->pkt_ptr, c);
+            off[k] = o;
+            len[k] = m->pkt_totallen;
+            id[k] = held_put(m);
+            if (id[k] == ~0ull) rc = PPE_ENOMEM;
+            else put = k + 1;
+            at[k++] = i;
+            o += ((size_t)c + 3u) & ~(size_t)3;
+        }
+        if (rc == PPE_OK && take_step_fail(1u)) rc = PPE_EIO;
+        if (rc == PPE_OK) {
+            const ppe_frag_batch_t in = {pkt, off, len, id, nf, 0u, g_df_now};
+            const ppe_defrag_out_t out = {st, of, win, dlen, d->frames, chain, &nd, ws, 0u};
+            rc = ppe_defrag_host(g_df, &in, &out, 0);
+        }
+        if (rc == PPE_OK) {
+            d->rm = nd ? (mbuf_t *)burst_alloc(sizeof(mbuf_t) * nd, 0) : NULL;
+            rmp = nd ? (mbuf_t **)burst_alloc(sizeof(mbuf_t *) * nd, 0) : NULL;
+            if (nd && (!d->rm || !rmp)) rc = PPE_ENOMEM;
+        }
+        for (uint32_t k = 0; rc == PPE_OK && k < nf; k++) {
+            const uint32_t i = at[k], s = st[k] & 0xffu;
+            switch (s) {
+                case PPE_DF_CACHED: case PPE_DF_SETUP_ERR:  /* cached: no hook (decode-defrag.c:391-392, 281-283) */
+                    d->disp[i] = DF_HELD;
+                    break;
+                case PPE_DF_REASM: {
+                    /* the reassembled mbuf as Frag_defrag_setup / _reasm leave it (:164-220, 241-276) */
+                    const uint32_t j = of[k];
+                    mbuf_t *r = &d->rm[j], *prev = NULL;
+                    memset(r, 0, sizeof *r);
+                    r->pkt_space = PKTBUF_SW;
+                    r->magic_flag = MBUF_MAGIC_NUM;
+                    r->pkt_ptr = d->frames + (size_t)j * rb;
+                    r->pkt_totallen = dlen[j];
+                    r->flags = PKT_FRAG_REASM_COMP;
+                    for (uint32_t p = 0; p < cm && chain[(size_t)j * cm + p] != ~0ull; p++) {
+                        mbuf_t *f = held_take(chain[(size_t)j * cm + p]);
+                        if (!f) continue;
+                        if (prev) prev->next = f;
+                        else {
+                            r->fragments = f;
+                            r->input_port = f->input_port;
+                        }
+                        f->next = NULL;
+                        prev = f;
+                    }
+                    rmp[j] = r;
+                    d->disp[i] = DF_DGRAM;
+                    d->dgram[i] = j;
+                    break;
+                }
+                case PPE_DF_NOT_FRAG:  /* (the two parsers agree on what a fragment is: not reached) as without Defrag */
+                    held_take(id[k]);
+                    break;
+                default:  /* FCB_FULL, HW2SW_ERR, DELETED, CACHE_FULL, DEFRAG_ERR: output_drop_proc */
+                    held_take(id[k]);
+                    d->disp[i] = s == PPE_DF_CACHE_FULL ? DF_DROP_LOG : DF_DROP;
+                    break;
+            }
+        }
+        if (rc == PPE_OK) d->nd = nd;
+    }
+    if (rc != PPE_OK) {
+        /* this burst's mbufs leave the registry (the caller drops them with the rest of the burst); everything else
+         * the table held goes with the table */
+        for (uint32_t k = 0; k < put; k++) held_take(id[k]);
+        if (g_df || g_held_cap) d->lost = defrag_reset_locked(&d->nlost);
+    }
+    pthread_mutex_unlock(&g_ctx_lock);
+    /* the datagrams: a second burst behind the first, in the order of their completing fragments, on the same path */
+    if (rc == PPE_OK && nd) {
+        rc = take_step_fail(2u) ? PPE_EIO : classify_mbufs(rmp, nd);
+        if (rc != PPE_OK) {
+            /* The chains' members are out of the registry already (the REASM loop took them).  Those of this burst are
+             * marked: the caller drops them with the rest of the burst, once, whatever they were before the chain took
+             * them (a fragment cached earlier in this burst, or the completing one).  Those of earlier bursts are in
+             * neither the registry nor this burst any more: they join what the table held. */
+            mbuf_t **outside = (mbuf_t **)malloc(sizeof(*outside) * ((size_t)nd * cm + 1u));
+            uint32_t nout = 0;
+            for (uint32_t j = 0; j < nd; j++)
+                for (mbuf_t *f = d->rm[j].fragments; f; f = f->next) {
+                    uint32_t i = 0;
+                    while (i < n && mb[i] != f) i++;
+                    if (i < n) d->disp[i] = DF_CHAIN;
+                    else if (outside) outside[nout++] = f;
+                }
+            pthread_mutex_lock(&g_ctx_lock);
+            /* this burst's fragments that are still cached leave the registry before it is emptied: dropped with the
+             * burst too.  (The lock was free during the classify step: a cached fragment that another thread's flush or
+             * aging took meanwhile went to a hook there, and is not dropped here again.) */
+            for (uint32_t k = 0; k < nf; k++)
+                if (d->disp[at[k]] == DF_HELD) {
+                    if (id[k] < g_held_cap && g_held[id[k]] == mb[at[k]]) held_take(id[k]);
+                    else d->disp[at[k]] = DF_GONE;
+                }
+            d->lost = defrag_reset_locked(&d->nlost);
+            pthread_mutex_unlock(&g_ctx_lock);
+            mbuf_t **all = (mbuf_t **)realloc(d->lost, sizeof(*all) * ((size_t)d->nlost + nout + 1u));
+            if (all) {
+                d->lost = all;
+                for (uint32_t k = 0; k < nout; k++) d->lost[d->nlost++] = outside[k];
+            }
+            free(outside);
+        }
+    }
+    free(at);
+    free(pkt);
+    free(off);
+    free(id);
+    free(len);
+    free(st);
+    free(of);
+    free(dlen);
+    free(win);
+    free(chain);
+    free(rmp);
+    return rc;
+}
+
 /* Take the burst's mbufs out (the burst is empty and reusable before any hook runs), classify, deliver.  The queued
  * array itself is taken, so a flush allocates nothing of its own: when the classify step cannot run (no context,
  * no memory, a GPU error), every taken mbuf still reaches the drop hook (decode.c:24-27; ppe_decode.h). */
@@ -581,13 +895,26 @@ static int flush_burst(burst_t *b) {
     mbuf_t **mb = b->m;
     b->m = NULL;
     b->n = b->alloc = 0;
-    const int rc = classify_mbufs(mb, n);
+    int rc = classify_mbufs(mb, n);
+    df_step_t df;
+    memset(&df, 0, sizeof df);
+    if (rc == PPE_OK && defrag_able == 1u) rc = defrag_mbufs(mb, n, &df);  /* (any other value is off) */
+    uint32_t calls = 0;
     for (uint32_t i = 0; i < n; i++) {
         mbuf_t *m = mb[i];
+        const uint8_t disp = (df.disp && (rc == PPE_OK || df.nd)) ? df.disp[i] : (uint8_t)DF_BY_VERDICT;
         if (rc != PPE_OK) {  /* undelivered: every packet ends in output_drop_proc (decode.c:24-27) */
+            if (disp != DF_GONE && out_drop) out_drop(m);
+            continue;
+        }
+        if (disp == DF_HELD) continue;  /* cached in its FCB: a later flush, DP_Defrag_Age or the release delivers it */
+        calls++;
+        if (disp == DF_DROP || disp == DF_DROP_LOG) {
+            if (disp == DF_DROP_LOG) DP_Log_Func(m);  /* cache full (decode-defrag.c:436) */
             if (out_drop) out_drop(m);
             continue;
         }
+        if (disp == DF_DGRAM) m = &df.rm[df.dgram[i]];  /* the datagram takes its completing fragment's place */
         const uint32_t v = m->ppe_verdict;
         switch (PPE_VERDICT_ACTION(v)) {
             case PPE_ACT_FW:
@@ -602,13 +929,16 @@ static int flush_burst(burst_t *b) {
                 break;
         }
     }
+    for (uint32_t i = 0; i < df.nlost; i++)  /* a failed defrag step: what its table held (ppe_decode.h) */
+        if (out_drop) out_drop(df.lost[i]);
+    df_step_free(&df);
     if (b == t_burst && !b->m) {  /* no hook queued anything meanwhile: the array goes back to the burst */
         b->m = mb;
         b->alloc = alloc;
     } else {
         free(mb);
     }
-    return rc == PPE_OK ? (int)n : rc;
+    return rc == PPE_OK ? (int)calls : rc;
 }
 
 int Decode_Flush(void) {

@@ -41,6 +41,7 @@
 #include <new>
 
 #include "ppe_hip.h"
+#include "ppe_internal.h"
 
 namespace {
 
@@ -143,7 +144,13 @@ __device__ __forceinline__ uint64_t lanemask_lt() {
 // frag_offset = (ip_off & 0x1fff) << 3, frag_len = L3 length − ihl*4 where the L3 length is what is left of
 // (uint16_t)pkt_totallen after the L2 header (Decode, decode.c:25; DecodeEthernet / DecodeVLAN len − 14 / − 4).
 // A frame that would not reach Defrag (any earlier drop, not a fragment, OSPF, frag_len 0) is PPE_DF_NOT_FRAG.
+// (csrc/ppe_defrag_small.hip builds each phase kernel's body as a function of its one-launch kernel: only the header
+// differs there, DESIGN.md §5.12, and this unit compiles the text it always did)
+#if defined(PPE_TU_DEFRAG_SMALL)
+__device__ __forceinline__ void df_parse_body(const DfArgs &a) {
+#else
 __global__ void __launch_bounds__(kBlock) df_parse_kernel(DfArgs a) {
+#endif
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= a.n) return;
     const uint8_t *p = a.pkt + a.off[i];
@@ -327,7 +334,11 @@ __device__ uint32_t wg_tile_prefix(const uint32_t *cnt, uint32_t t0, uint32_t ti
 // inclusive prefix.  Words carry the call's epoch, so the array needs no clearing between calls.  The per-tile counts
 // are kept for the sort's first pass (the running-count update).  The running count and free-stack top are read as
 // they stood before this batch: that histogram pass, which runs next, moves them past this batch's admissions.
+#if defined(PPE_TU_DEFRAG_SMALL)
+__device__ __forceinline__ void df_admit_body(const DfArgs &a) {
+#else
 __global__ void __launch_bounds__(kBlock) df_admit_kernel(DfArgs a) {
+#endif
     __shared__ uint32_t wc[kBlock / 64], wbase;
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     const uint32_t w = threadIdx.x >> 6;
@@ -445,7 +456,11 @@ constexpr uint32_t kGroupStride = DF_PROC_WIN;     // words per group in gslot (
 // (claim order, sorted back into batch order by the group's head in df_process_kernel) while slots remain; past
 // kGroupSlots it is only counted (the head then finds every member from gkey).  Also: the parsed record's words 6-7 for the process kernel, the completion tile counts cleared,
 // and (workgroup 0) the running count and free-stack top moved past this batch's admissions.
+#if defined(PPE_TU_DEFRAG_SMALL)
+__device__ __forceinline__ void df_group_body(const DfArgs &a) {
+#else
 __global__ void __launch_bounds__(kBlock) df_group_kernel(DfArgs a) {
+#endif
     const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
     if (blockIdx.x == 0) {
         // after the admission kernel: the creators of this batch (the tile counts it ranked) move the running count
@@ -720,7 +735,11 @@ __device__ __forceinline__ void df_process_one(const DfArgs &a, uint32_t j, uint
     a.rts[r] = a.now;
 }
 
+#if defined(PPE_TU_DEFRAG_SMALL)
+__device__ __forceinline__ void df_process_body(const DfArgs &a) {
+#else
 __global__ void __launch_bounds__(kBlock) df_process_kernel(DfArgs a) {
+#endif
     __shared__ uint32_t cdesc[16][kBlock];
     __shared__ uint32_t cidx[16][kBlock];
     __shared__ uint32_t wg[PPE_DF__COUNT + 1];   // per-status counts + teardrops of this workgroup
@@ -802,7 +821,11 @@ __device__ __forceinline__ void df_stash_one(const DfArgs &a, uint32_t i) {
 }
 
 // ---- place: datagram index of each completing fragment, in index order ------------------------------------------------
+#if defined(PPE_TU_DEFRAG_SMALL)
+__device__ __forceinline__ void df_place_body(const DfArgs &a) {
+#else
 __global__ void __launch_bounds__(kBlock) df_place_kernel(DfArgs a) {
+#endif
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     const uint32_t t0 = blockIdx.x * (kBlock / 64), w = threadIdx.x >> 6;
     uint32_t nd = 0;
@@ -1014,6 +1037,9 @@ __device__ __forceinline__ void df_assemble_slot(const DfArgs &a, uint32_t j, ui
 #ifndef DF_ASM_WAVES
 #define DF_ASM_WAVES 0   // > 0: the compiler is held to this many waves per SIMD (A/B builds)
 #endif
+#if defined(PPE_TU_DEFRAG_SMALL)
+__device__ __forceinline__ void df_assemble_body(const DfArgs &a, const uint32_t w) {   // w: this wave's position
+#else
 #if DF_ASM_WAVES > 0
 __global__ void __launch_bounds__(kSlotBlock) __attribute__((amdgpu_waves_per_eu(DF_ASM_WAVES, DF_ASM_WAVES)))
 #else
@@ -1021,6 +1047,7 @@ __global__ void __launch_bounds__(kSlotBlock)
 #endif
 df_assemble_kernel(DfArgs a) {
     const uint32_t w = blockIdx.x * (kSlotBlock / 64) + (threadIdx.x >> 6);
+#endif
     if (w >= a.n) return;
     const uint32_t nd = (uint32_t)a.ctl[C_NDGRAM];
     if (w < nd) {
@@ -1033,6 +1060,49 @@ df_assemble_kernel(DfArgs a) {
     }
 }
 
+#if defined(PPE_TU_DEFRAG_SMALL)
+// ---- one launch for a small batch (csrc/ppe_defrag_small.hip) ----------------------------------------
+// One workgroup of kBlock threads runs the six phases above in order for 1 <= n <= PPE_DEFRAG_SMALL_CUTOFF <= kBlock:
+// every phase body is the text of its kernel with blockIdx.x == 0, which is what that kernel's one workgroup runs for
+// such a batch (the assemble kernel's n / 4 workgroups become this workgroup's waves stepping over the positions).
+// Between two phases: every wave drains its stores and atomics, the workgroup barrier, then an agent-scope
+// acquire-release fence in every wave.  The phases hand words over through L2 (claims by CAS, tickets and counts by
+// atomics) and read them with plain loads, which would hit the L1 lines an earlier phase's loads left behind without
+// the acquire (MI355X_MICROARCH.md, "Stale without an agent-scope acquire"); the table of words is in DESIGN.md §5.12.
+// No wait on another workgroup: the admission look-back of workgroup 0 has no predecessor (its loop runs 0 times).
+__device__ __forceinline__ void df_phase_sync() {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");
+}
+
+__global__ void __launch_bounds__(kBlock) ppe_defrag_small_kernel(DfArgs a) {
+    static_assert(PPE_DEFRAG_SMALL_CUTOFF <= kBlock, "one fragment per thread: the phase bodies index by threadIdx.x");
+    static_assert(PPE_DEFRAG_SMALL_BLOCK == kBlock, "the planner's view of the workgroup");
+    df_parse_body(a);      // frec, fslot; claims: tstate (CAS), creator (atomicMin)
+    df_phase_sync();
+    df_admit_body(a);      // tcnt; tkey, rhdr, rts, tstate LIVE / TOMB
+    df_phase_sync();
+    df_group_body(a);      // ctl; gkey, frec words 6-7, gcnt (tickets), gslot, dcnt = 0
+    df_phase_sync();
+    df_process_body(a);    // status, inserted, dgrec, rhdr, rdesc, dcnt (atomics), ctl status counts
+    df_phase_sync();
+    df_place_body(a);      // ctl[C_NDGRAM], n_dgram, dgram_of, plan, dgram_len past the count
+    df_phase_sync();
+    // stash + assemble: the waves step over the batch positions (bound: n <= kBlock, kBlock / 64 positions per round)
+    for (uint32_t w = threadIdx.x >> 6; w < a.n; w += kBlock / 64) df_assemble_body(a, w);
+}
+
+}  // namespace
+
+extern "C" int ppe_launch_defrag_small(const void *args, uint32_t bytes, void *stream) {
+    if (bytes != sizeof(DfArgs)) return (int)hipErrorInvalidValue;   // (both units build DfArgs from this file)
+    const DfArgs &a = *(const DfArgs *)args;
+    if (a.n < 1u || a.n > kBlock) return (int)hipErrorInvalidValue;   // (one fragment per thread)
+    hipLaunchKernelGGL(ppe_defrag_small_kernel, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+#else
 // ---- aging + table rebuild (one workgroup) ----------------------------------------------------------------------------
 __global__ void __launch_bounds__(kScanT) df_age_kernel(DfArgs a) {
     __shared__ uint32_t nfreed, ndropped;
@@ -1115,6 +1185,17 @@ struct ppe_defrag_table {
     unsigned long long *h_ctl = nullptr;   // pinned
     unsigned long long *h_err = nullptr;   // pinned, device-mapped: a batch's admission look-back failed
     uint32_t epoch = 0;                    // admission look-back tag of the last call
+    uint32_t small_upto = 0;               // batches of at most this many fragments take the one launch (PPE_DEFRAG_SMALL)
+    uint32_t last_kind = 0, last_launches = 0;   // the last batch's shape (ppe_defrag_launch_info)
+    // ppe_defrag_host: its ordered stream and the staging of one chunk (grown on demand, freed with the table)
+    hipStream_t hs = nullptr;
+    uint8_t *h_in = nullptr, *d_in = nullptr;     // offsets, ids, lengths, frames (pinned / device)
+    size_t in_cap = 0;
+    uint8_t *h_res = nullptr, *d_res = nullptr;   // datagram count, status, dgram_of, dgram_len (pinned / device)
+    uint8_t *d_hdr = nullptr, *d_pkt = nullptr;   // a chunk's datagram rows: windows, whole frames, fragment ids
+    uint64_t *d_frags = nullptr;
+    uint32_t res_cap = 0, row_cap = 0;            // fragments the result staging holds; datagram rows the row staging holds
+    bool rows_pkt = false, rows_frags = false;
     char err[256] = {0};
 };
 
@@ -1136,6 +1217,68 @@ bool dalloc(ppe_defrag_t *d, T **p, size_t count) {
     if (hipMalloc(&q, std::max<size_t>(count * sizeof(T), 64)) != hipSuccess) return false;
     d->allocs[d->nalloc++] = q;
     *p = (T *)q;
+    return true;
+}
+
+void df_host_free(ppe_defrag_t *d) {
+    if (d->h_in) (void)hipHostFree(d->h_in);
+    if (d->h_res) (void)hipHostFree(d->h_res);
+    for (void *p : {(void *)d->d_in, (void *)d->d_res, (void *)d->d_hdr, (void *)d->d_pkt, (void *)d->d_frags})
+        if (p) (void)hipFree(p);
+    d->h_in = d->d_in = d->h_res = d->d_res = d->d_hdr = d->d_pkt = nullptr;
+    d->d_frags = nullptr;
+    d->in_cap = 0;
+    d->res_cap = d->row_cap = 0;
+    d->rows_pkt = d->rows_frags = false;
+}
+
+// ppe_defrag_host's staging for a chunk of c fragments whose input blob takes in_bytes, with whole frames and / or
+// fragment-id rows wanted: grown, never shrunk
+constexpr size_t kResHead = 64;   // the result blob's first bytes: the chunk's datagram count
+bool df_host_reserve(ppe_defrag_t *d, uint32_t c, size_t in_bytes, bool want_pkt, bool want_frags) {
+    if (!d->hs && hipStreamCreate(&d->hs) != hipSuccess) return false;
+    if (in_bytes > d->in_cap) {
+        const size_t cap = std::max(in_bytes, d->in_cap * 2);
+        if (d->h_in) (void)hipHostFree(d->h_in);
+        if (d->d_in) (void)hipFree(d->d_in);
+        d->h_in = d->d_in = nullptr;
+        d->in_cap = 0;
+        if (hipHostMalloc((void **)&d->h_in, cap, hipHostMallocDefault) != hipSuccess ||
+            hipMalloc((void **)&d->d_in, cap) != hipSuccess)
+            return false;
+        d->in_cap = cap;
+    }
+    if (c > d->res_cap) {
+        const uint32_t cap = std::min(std::max(c, d->res_cap * 2), d->cfg.max_batch);
+        if (d->h_res) (void)hipHostFree(d->h_res);
+        if (d->d_res) (void)hipFree(d->d_res);
+        d->h_res = d->d_res = nullptr;
+        d->res_cap = 0;
+        if (hipHostMalloc((void **)&d->h_res, kResHead + (size_t)cap * 12, hipHostMallocDefault) != hipSuccess ||
+            hipMalloc((void **)&d->d_res, kResHead + (size_t)cap * 12) != hipSuccess)
+            return false;
+        d->res_cap = cap;
+    }
+    // a chunk completes at most one datagram per FCB record
+    const uint32_t rows = std::min(c, d->cfg.fcb_max);
+    if (rows > d->row_cap || (want_pkt && !d->rows_pkt) || (want_frags && !d->rows_frags)) {
+        const uint32_t cap = std::min(std::max(rows, d->row_cap * 2), std::min(d->cfg.max_batch, d->cfg.fcb_max));
+        want_pkt = want_pkt || d->rows_pkt;
+        want_frags = want_frags || d->rows_frags;
+        for (void *p : {(void *)d->d_hdr, (void *)d->d_pkt, (void *)d->d_frags})
+            if (p) (void)hipFree(p);
+        d->d_hdr = d->d_pkt = nullptr;
+        d->d_frags = nullptr;
+        d->row_cap = 0;
+        d->rows_pkt = d->rows_frags = false;
+        if (hipMalloc((void **)&d->d_hdr, (size_t)cap * 128) != hipSuccess ||
+            (want_pkt && hipMalloc((void **)&d->d_pkt, (size_t)cap * d->cfg.reasm_buf_bytes + 64) != hipSuccess) ||
+            (want_frags && hipMalloc((void **)&d->d_frags, (size_t)cap * d->cfg.cache_max * 8) != hipSuccess))
+            return false;
+        d->row_cap = cap;
+        d->rows_pkt = want_pkt;
+        d->rows_frags = want_frags;
+    }
     return true;
 }
 
@@ -1210,6 +1353,11 @@ int ppe_defrag_create(ppe_ctx_t *ctx, const ppe_defrag_cfg_t *cfg, ppe_defrag_t 
     a.look_fail_wg = ~0u;
     if (const char *e = getenv("PPE_DF_LOOK_FAIL"))  // test hook: this workgroup index fails its look-back
         a.look_fail_wg = (uint32_t)atoi(e);
+    // PPE_DEFRAG_SMALL: 0 is the A/B switch (every batch on the six launches); N > 1 is a diagnostic
+    // (tools/ab_defrag_small.py measures past the cutoff with it, the tests run the kernel at every size its workgroup
+    // holds).  The planner turns it into the table's largest one-launch batch (csrc/launch_plan.cpp).
+    const char *sm = getenv("PPE_DEFRAG_SMALL");
+    d->small_upto = ppe_defrag_small_upto_from_env(sm ? std::max(0, atoi(sm)) : -1);
     const uint32_t span = std::max(std::max(std::max(ns, a.nlook), std::max(c.fcb_max, (uint32_t)C_WORDS)), mb);
     hipLaunchKernelGGL(df_init_kernel, dim3(blocks(span, 256)), dim3(256), 0, 0, a);
     if (hipDeviceSynchronize() != hipSuccess) {
@@ -1227,6 +1375,8 @@ int ppe_defrag_destroy(ppe_defrag_t *d) {
     for (int k = 0; k < d->nalloc; ++k) (void)hipFree(d->allocs[k]);
     if (d->h_ctl) (void)hipHostFree(d->h_ctl);
     if (d->h_err) (void)hipHostFree(d->h_err);
+    df_host_free(d);
+    if (d->hs) (void)hipStreamDestroy(d->hs);
     delete d;
     return PPE_OK;
 }
@@ -1265,10 +1415,20 @@ int ppe_defrag(ppe_defrag_t *d, const ppe_frag_batch_t *in, const ppe_defrag_out
     a.dgram_frags = out->dgram_frags;
     a.n_dgram = out->n_dgram;
     a.hdr_stride = out->hdr_stride;
-    const uint32_t g = blocks(a.n, kBlock);
-    hipLaunchKernelGGL(df_parse_kernel, dim3(g), dim3(kBlock), 0, s, a);
     if (++d->epoch == 0) d->epoch = 1;   // (0 is the cleared array's tag)
     a.epoch = d->epoch;
+    // a small batch: the six phases in one launch of one workgroup (csrc/ppe_defrag_small.hip), unless the table was
+    // created under PPE_DEFRAG_SMALL=0 or the look-back test hook is armed (workgroup 0 never looks back)
+    if (ppe_pick_defrag_small_upto(a.n, d->small_upto, a.look_fail_wg != ~0u)) {
+        d->last_kind = 1;
+        d->last_launches = 1;
+        const int e = ppe_launch_defrag_small(&a, (uint32_t)sizeof(a), (void *)s);
+        return e == (int)hipSuccess ? PPE_OK : dfail(d, PPE_EIO, "ppe_defrag: %s", hipGetErrorString((hipError_t)e));
+    }
+    d->last_kind = 0;
+    d->last_launches = 6;
+    const uint32_t g = blocks(a.n, kBlock);
+    hipLaunchKernelGGL(df_parse_kernel, dim3(g), dim3(kBlock), 0, s, a);
     hipLaunchKernelGGL(df_admit_kernel, dim3(g), dim3(kBlock), 0, s, a);
     d->base.look_fail_wg = ~0u;   // (the test hook fails one call's look-back, the first)
     hipLaunchKernelGGL(df_group_kernel, dim3(g), dim3(kBlock), 0, s, a);
@@ -1276,6 +1436,96 @@ int ppe_defrag(ppe_defrag_t *d, const ppe_frag_batch_t *in, const ppe_defrag_out
     hipLaunchKernelGGL(df_place_kernel, dim3(g), dim3(kBlock), 0, s, a);
     hipLaunchKernelGGL(df_assemble_kernel, dim3(blocks(a.n, kSlotBlock / 64)), dim3(kSlotBlock), 0, s, a);
     return launched(d, "ppe_defrag");
+}
+
+int ppe_defrag_launch_info(ppe_defrag_t *d, uint32_t *kind, uint32_t *launches) {
+    if (!d) return PPE_EINVAL;
+    if (kind) *kind = d->last_kind;
+    if (launches) *launches = d->last_launches;
+    return PPE_OK;
+}
+
+int ppe_defrag_host(ppe_defrag_t *d, const ppe_frag_batch_t *in, const ppe_defrag_out_t *out, uint32_t chunk) {
+    if (!d || !in || !out) return PPE_EINVAL;
+    if (in->n && (!in->pkt || !in->off || !in->len || !out->status || !out->dgram_hdr || !out->dgram_len))
+        return dfail(d, PPE_EINVAL, "pkt/off/len and status/dgram_hdr/dgram_len are required");
+    if (out->hdr_stride != 64 && out->hdr_stride != 128) return dfail(d, PPE_EINVAL, "hdr_stride must be 64 or 128");
+    if (hipSetDevice(d->device) != hipSuccess) return PPE_ENODEV;
+    if (__atomic_load_n(d->h_err, __ATOMIC_ACQUIRE)) {   // (as ppe_defrag: reported once, before anything is written)
+        __atomic_store_n(d->h_err, 0ull, __ATOMIC_RELAXED);
+        return dfail(d, PPE_EIO, "ppe_defrag_host: an earlier batch's admission look-back timed out: the FCBs of that "
+                                 "batch's workgroup were not created (its fragments' results are wrong)");
+    }
+    if (!chunk || chunk > d->cfg.max_batch) chunk = d->cfg.max_batch;
+    // a frame's bytes past frag_buf_bytes are never read: the parse reads its first 44, and only a held fragment
+    // (frame <= frag_buf_bytes, PACKET_HW2SW) is copied
+    const uint32_t keep = std::max(d->cfg.frag_buf_bytes, 64u);
+    const uint32_t stride = out->hdr_stride, cm = d->cfg.cache_max;
+    uint32_t base = 0;   // datagrams of the chunks before this one: their indices run on
+    for (uint32_t c0 = 0; c0 < in->n; c0 += chunk) {
+        const uint32_t c = std::min(chunk, in->n - c0);
+        const size_t o_id = (size_t)c * 8, o_len = o_id + (size_t)c * 8, o_frames = (o_len + (size_t)c * 4 + 7) & ~(size_t)7;
+        size_t bytes = o_frames;
+        for (uint32_t i = 0; i < c; ++i) bytes += ((size_t)std::min(in->len[c0 + i], keep) + 3) & ~(size_t)3;
+        bytes += 64;   // (whole aligned dwords are read around a frame's last byte)
+        if (!df_host_reserve(d, c, bytes, out->dgram_pkt != nullptr, out->dgram_frags != nullptr))
+            return dfail(d, PPE_ENOMEM, "ppe_defrag_host: staging for %u fragments", c);
+        uint64_t *h_off = (uint64_t *)d->h_in, *h_id = (uint64_t *)(d->h_in + o_id);
+        uint32_t *h_len = (uint32_t *)(d->h_in + o_len);
+        size_t at = o_frames;
+        for (uint32_t i = 0; i < c; ++i) {
+            const uint32_t len = in->len[c0 + i], cp = std::min(len, keep);
+            h_off[i] = at;
+            h_id[i] = in->id ? in->id[c0 + i] : (uint64_t)(c0 + i);
+            h_len[i] = len;
+            memcpy(d->h_in + at, in->pkt + in->off[c0 + i], cp);
+            at += ((size_t)cp + 3) & ~(size_t)3;
+        }
+        memset(d->h_in + at, 0, 64);
+        if (hipMemcpyAsync(d->d_in, d->h_in, bytes, hipMemcpyHostToDevice, d->hs) != hipSuccess)
+            return dfail(d, PPE_EIO, "ppe_defrag_host: copy to the device failed");
+        ppe_frag_batch_t bin{};
+        bin.pkt = d->d_in;
+        bin.off = (const uint64_t *)d->d_in;
+        bin.id = (const uint64_t *)(d->d_in + o_id);
+        bin.len = (const uint32_t *)(d->d_in + o_len);
+        bin.n = c;
+        bin.now_seconds = in->now_seconds;
+        ppe_defrag_out_t bout{};
+        uint32_t *r = (uint32_t *)(d->d_res + kResHead);
+        bout.n_dgram = (uint32_t *)d->d_res;
+        bout.status = r;
+        bout.dgram_of = r + c;
+        bout.dgram_len = r + 2 * (size_t)c;
+        bout.dgram_hdr = d->d_hdr;
+        bout.dgram_pkt = out->dgram_pkt ? d->d_pkt : nullptr;
+        bout.dgram_frags = out->dgram_frags ? d->d_frags : nullptr;
+        bout.hdr_stride = stride;
+        const int rc = ppe_defrag(d, &bin, &bout, (void *)d->hs);
+        if (rc != PPE_OK) return rc;
+        if (hipMemcpyAsync(d->h_res, d->d_res, kResHead + (size_t)c * 12, hipMemcpyDeviceToHost, d->hs) != hipSuccess ||
+            hipStreamSynchronize(d->hs) != hipSuccess)
+            return dfail(d, PPE_EIO, "ppe_defrag_host: the chunk at %u failed", c0);
+        const uint32_t nd = *(const uint32_t *)d->h_res;
+        const uint32_t *hr = (const uint32_t *)(d->h_res + kResHead);
+        if (nd > std::min(c, d->cfg.fcb_max))   // (before anything of this chunk is written)
+            return dfail(d, PPE_EIO, "ppe_defrag_host: %u datagrams from %u fragments", nd, c);
+        memcpy(out->status + c0, hr, (size_t)c * 4);
+        if (out->dgram_of)
+            for (uint32_t i = 0; i < c; ++i) out->dgram_of[c0 + i] = hr[c + i] == kNone ? kNone : hr[c + i] + base;
+        if (nd) {   // only the rows of datagrams that exist come back
+            memcpy(out->dgram_len + base, hr + 2 * (size_t)c, (size_t)nd * 4);
+            if (hipMemcpy(out->dgram_hdr + (size_t)base * stride, d->d_hdr, (size_t)nd * stride, hipMemcpyDeviceToHost) != hipSuccess ||
+                (out->dgram_pkt && hipMemcpy(out->dgram_pkt + (size_t)base * d->cfg.reasm_buf_bytes, d->d_pkt,
+                                             (size_t)nd * d->cfg.reasm_buf_bytes, hipMemcpyDeviceToHost) != hipSuccess) ||
+                (out->dgram_frags && hipMemcpy(out->dgram_frags + (size_t)base * cm, d->d_frags, (size_t)nd * cm * 8,
+                                               hipMemcpyDeviceToHost) != hipSuccess))
+                return dfail(d, PPE_EIO, "ppe_defrag_host: copy of %u datagrams failed", nd);
+        }
+        base += nd;
+    }
+    if (out->n_dgram) *out->n_dgram = base;
+    return PPE_OK;
 }
 
 int ppe_defrag_age(ppe_defrag_t *d, uint64_t now_seconds, uint64_t timeout_seconds, uint64_t *dropped, uint32_t max,
@@ -1331,3 +1581,4 @@ int ppe_defrag_info(ppe_defrag_t *d, ppe_defrag_info_t *info) {
 }
 
 }  // extern "C"
+#endif  // !PPE_TU_DEFRAG_SMALL

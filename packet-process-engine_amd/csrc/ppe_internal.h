@@ -151,6 +151,14 @@ struct ppe_flow_small_tail {
     uint32_t pad;
 };
 
+/* ---- one launch for small fragment batches (csrc/ppe_defrag_small.hip) ----
+ * A ppe_defrag batch of 1 <= n <= PPE_DEFRAG_SMALL_CUTOFF fragments runs its six phases in one launch of one
+ * PPE_DEFRAG_SMALL_BLOCK-thread workgroup instead of six launches sized for 65,536-fragment batches
+ * (ppe_pick_defrag_small).  At most the workgroup's threads (one fragment per thread in the per-fragment phases), and
+ * never above the largest size at which tools/ab_defrag_small.py's measurement supports it. */
+#define PPE_DEFRAG_SMALL_CUTOFF 4u
+#define PPE_DEFRAG_SMALL_BLOCK 256
+
 /* batches per launch whose descriptors travel in the kernel arguments (32 × 96 B); a launch over more batches reads
  * them from a device descriptor ring (ppe_kargs.ring) */
 #define PPE_MAX_BATCH 32
@@ -472,6 +480,19 @@ uint32_t ppe_pick_attack_flow(int flow, int flow_attached);
  * (small_allowed: not created under PPE_FLOW_SMALL=0, the post-launch failure hook not armed) and no monitors are
  * flow-attached (their syncount count lives in the post kernel); else 0, the two launches */
 uint32_t ppe_pick_flow_small(uint32_t n, int small_allowed, int atk_flow_attached);
+/* 1: the ppe_defrag batch of n fragments takes the one-launch kernel: 1 <= n <= PPE_DEFRAG_SMALL_CUTOFF, the table
+ * allows it (small_allowed: not created under PPE_DEFRAG_SMALL=0) and the admission look-back's failure hook
+ * (PPE_DF_LOOK_FAIL) is not armed; else 0, the six launches */
+uint32_t ppe_pick_defrag_small(uint32_t n, int small_allowed, int look_fail_armed);
+/* the planner's general form, which ppe_defrag calls: the one launch for 1 <= n <= upto (clamped to
+ * PPE_DEFRAG_SMALL_BLOCK) unless the hook is armed; upto is the table's, from PPE_DEFRAG_SMALL at ppe_defrag_create
+ * (`value`: its integer, -1 when unset): unset or 1 the cutoff, 0 none, N > 1 min(N, PPE_DEFRAG_SMALL_BLOCK), a
+ * diagnostic for measuring and testing the kernel past the cutoff */
+uint32_t ppe_pick_defrag_small_upto(uint32_t n, uint32_t upto, int look_fail_armed);
+uint32_t ppe_defrag_small_upto_from_env(int value);
+/* the one-launch defrag kernel (csrc/ppe_defrag_small.hip): one workgroup of PPE_DEFRAG_SMALL_BLOCK threads over the
+ * batch in `args` (csrc/ppe_defrag.hip's argument block, `bytes` its size).  Returns hipError_t */
+int ppe_launch_defrag_small(const void *args, uint32_t bytes, void *stream);
 /* how a flow batch of n packets runs with respect to the port-scan detector: PPE_FPS_PLAIN today's kernels (no table
  * flow-attached, or its detector off: portscan_able == 0), PPE_FPS_KERNEL the one-launch kernel with the detector
  * inside (1 <= n <= PPE_FLOW_PS_MAX), PPE_FPS_REFUSE a larger batch (PPE_ENOTSUP before anything is touched) */

@@ -334,7 +334,9 @@ EXPORTS = [
     "ppe_format_pkt_stat_ex", "ppe_format_flow_stat_ex",
     "ppe_steer_partition", "ppe_gather_rows", "ppe_scatter_rows",
     "ppe_defrag_create", "ppe_defrag_destroy", "ppe_defrag", "ppe_defrag_age", "ppe_defrag_info",
-    "ppe_defrag_last_error",
+    "DP_Defrag_Clock", "DP_Defrag_Age", "DP_Defrag_Table",
+    "ppe_defrag_last_error", "ppe_defrag_launch_info", "ppe_defrag_host", "ppe_pick_defrag_small",
+    "ppe_pick_defrag_small_upto", "ppe_defrag_small_upto_from_env",
     "ppe_stream_tcp_set", "ppe_stream_tcp_get", "ppe_stream_counters_read", "ppe_stream_counters_clear",
     "ppe_format_tcpstream_stat",
     "ppe_portscan_create", "ppe_portscan_destroy", "ppe_portscan_attach", "ppe_portscan_clock", "ppe_portscan_set",
@@ -453,6 +455,14 @@ def _open(p: Path, mode, strict: bool = True) -> C.CDLL:
         "ppe_defrag_age": ([vp, u64, u64, vp, u32, C.POINTER(u32), C.POINTER(u32)], C.c_int),
         "ppe_defrag_info": ([vp, C.POINTER(DefragInfo)], C.c_int),
         "ppe_defrag_last_error": ([vp], C.c_char_p),
+        "ppe_defrag_launch_info": ([vp, C.POINTER(u32), C.POINTER(u32)], C.c_int),
+        "ppe_defrag_host": ([vp, C.POINTER(FragBatch), C.POINTER(DefragOut), u32], C.c_int),
+        "ppe_pick_defrag_small": ([u32, C.c_int, C.c_int], u32),
+        "ppe_pick_defrag_small_upto": ([u32, u32, C.c_int], u32),
+        "ppe_defrag_small_upto_from_env": ([C.c_int], u32),
+        "DP_Defrag_Clock": ([u64], None),
+        "DP_Defrag_Age": ([u64, C.POINTER(u64)], C.c_int),
+        "DP_Defrag_Table": ([], vp),
         "ppe_stream_tcp_set": ([vp, C.POINTER(StreamTcpCfg)], C.c_int),
         "ppe_stream_tcp_get": ([vp, C.POINTER(StreamTcpCfg)], C.c_int),
         "ppe_stream_counters_read": ([vp, C.POINTER(StreamCounters)], C.c_int),

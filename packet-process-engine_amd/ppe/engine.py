@@ -393,6 +393,38 @@ class Defrag:
                           g("dgram_frags"), g("n_dgram"), out["dgram_hdr"].shape[1], 0)
         self._check(self.lib.ppe_defrag(self.h, C.byref(b), C.byref(o), s.cuda_stream), "ppe_defrag")
 
+    def launch_info(self):
+        """(kind, launches) of the last ppe_defrag batch: (1, 1) the one-launch kernel, (0, 6) the six launches."""
+        k, l = C.c_uint32(0), C.c_uint32(0)
+        self._check(self.lib.ppe_defrag_launch_info(self.h, C.byref(k), C.byref(l)), "ppe_defrag_launch_info")
+        return k.value, l.value
+
+    def run_host(self, pkt, off, lens, now: int, ids=None, chunk: int = 0, hdr_stride: int = 128, full: bool = True,
+                 guard: int = 0):
+        """ppe_defrag_host on numpy arrays in host memory: pkt (u8 arena), off (u64), lens (u32), ids (u64, optional).
+        Returns a dict of numpy outputs (status, dgram_of, dgram_hdr, dgram_len, dgram_frags, n_dgram, and dgram_pkt
+        when full), each with `guard` more entries / rows behind its n, filled with 0xA5 bytes."""
+        pkt = np.ascontiguousarray(pkt, np.uint8)
+        off = np.ascontiguousarray(off, np.uint64)
+        lens = np.ascontiguousarray(lens, np.uint32)
+        ids = np.ascontiguousarray(ids, np.uint64) if ids is not None else None
+        n, cm = int(lens.size), self.info_["cache_max"]
+        rows = n + guard
+        mk = lambda shape, dt: np.frombuffer(bytearray(b"\xa5" * (int(np.prod(shape)) * np.dtype(dt).itemsize)),
+                                             dtype=dt).reshape(shape)
+        out = dict(status=mk((rows,), np.uint32), dgram_of=mk((rows,), np.uint32),
+                   dgram_hdr=mk((rows, hdr_stride), np.uint8), dgram_len=mk((rows,), np.uint32),
+                   dgram_frags=mk((rows, cm), np.uint64), n_dgram=mk((1 + guard,), np.uint32))
+        if full:
+            out["dgram_pkt"] = mk((rows, self.info_["reasm_buf_bytes"]), np.uint8)
+        b = abi.FragBatch(pkt.ctypes.data, off.ctypes.data, lens.ctypes.data,
+                          ids.ctypes.data if ids is not None else None, n, 0, int(now))
+        g = lambda k: out[k].ctypes.data if k in out else None
+        o = abi.DefragOut(g("status"), g("dgram_of"), g("dgram_hdr"), g("dgram_len"), g("dgram_pkt"),
+                          g("dgram_frags"), g("n_dgram"), hdr_stride, 0)
+        self._check(self.lib.ppe_defrag_host(self.h, C.byref(b), C.byref(o), int(chunk)), "ppe_defrag_host")
+        return out
+
     def age(self, now: int, timeout: int = 20):
         """Frag_defrag_timeout: returns (dropped fragment ids, FCBs freed)."""
         cap = self.info_["fcb_max"] * self.info_["cache_max"]
