@@ -43,7 +43,8 @@ extern "C" {
  * detector (ppe_portscan_*, status 24, ppe_format_pkt_stat_ps, ppe_format_fw_config), off until a table is attached;
  * the land / SYN-flood / UDP-flood monitors (ppe_attack_*, statuses 25-28, ppe_format_attack_stat,
  * ppe_format_pkt_stat_atk), off until an object is attached; ppe_classify_host_ordered and
- * ppe_portscan_prepass_info; ppe_classify_flow_host and ppe_flow_launch_info; ppe_flow_portscan_attach, _max, _rounds */
+ * ppe_portscan_prepass_info; ppe_classify_flow_host and ppe_flow_launch_info; ppe_flow_portscan_attach, _max, _rounds;
+ * ppe_flow_combine */
 #define PPE_ABI_VERSION 8
 
 /* error codes (negative return values) */
@@ -444,8 +445,9 @@ int  ppe_classify_flow(ppe_ctx_t *ctx, const ppe_batch_t *in, const ppe_result_t
 int  ppe_classify_flow_host(ppe_ctx_t *ctx, const ppe_batch_t *in, const ppe_result_t *out, const ppe_cfg_t *cfg,
                             uint32_t chunk);
 /* What the last flow batch of the context's table took: *kind 1 and *launches 1 (the one-launch kernel), 2 and 1 (the
- * one-launch kernel with the port-scan detector inside, ppe_flow_portscan_attach), or 0 and 2; 0 and 0 before the first
- * batch.  NULL arguments: PPE_EINVAL. */
+ * one-launch kernel with the port-scan detector inside, ppe_flow_portscan_attach), 3 and 1 (that kernel with the
+ * flow-attached attack monitors in it as well, ppe_flow_combine), or 0 and 2; 0 and 0 before the first batch.  NULL
+ * arguments: PPE_EINVAL. */
 int  ppe_flow_launch_info(ppe_ctx_t *ctx, uint32_t *kind, uint32_t *launches);
 /* FlowAgeTimeoutCB: delete flows with now > last_seen && now - last_seen > timeout_seconds; *deleted = count
  * (may be NULL).  Synchronises. */
@@ -682,7 +684,7 @@ const char *ppe_portscan_last_error(ppe_portscan_t *ps);
  * One batch takes at most ppe_flow_portscan_max() packets (one launch of one workgroup, ppe_flow_launch_info kind 2);
  * a larger device batch returns PPE_ENOTSUP before anything is touched (ppe_classify_flow_host chunks host batches of
  * any size); n above the port-scan table's max_batch: PPE_EINVAL.  Also PPE_ENOTSUP before anything is touched: attack
- * monitors flow-attached at the same time, and stream tracking.  With able = 0 or nothing flow-attached the flow path is
+ * monitors flow-attached at the same time unless ppe_flow_combine is on (below), and stream tracking.  With able = 0 or nothing flow-attached the flow path is
  * byte for byte what it is without this interface, at every size.  The stateless calls do not see a flow-attached table.
  * A table sits on at most one of the two attachment points: attaching one that the other point holds is PPE_EINVAL
  * (detach first), as is a table of another context; ppe_portscan_destroy detaches from whichever holds it. */
@@ -692,6 +694,30 @@ uint32_t ppe_flow_portscan_max(void);
  * inside (0: none yet, or no packet of it was pending).  A plain flow batch (able 0, nothing flow-attached) does not
  * change it: check ppe_flow_launch_info for kind 2 first.  Synchronises. */
 int  ppe_flow_portscan_rounds(ppe_ctx_t *ctx, uint32_t *rounds);
+/* ---- The monitors and the detector together on the flow-table path: the reference's whole order, Decode -> DecodeIPV4 /
+ * DecodeTCP (land, SYN-flood, SYN-count, UDP-flood monitors) -> FlowHandlePacket -> FlowFind | miss -> syn_check ->
+ * PortScan_Detect -> DP_Acl_Lookup -> FlowAdd (syncount_accum) ----
+ * 0 (a new context): ppe_classify_flow refuses a batch while a port-scan table with able 1 and attack monitors are both
+ * flow-attached (PPE_ENOTSUP, as before).  1: such a batch runs the reference's whole path in one launch
+ * (ppe_flow_launch_info kind 3), exactly as one core running the batch in index order, packet i seeing all three
+ * states as packets 0..i-1 left them:
+ *   - the monitors first, for every packet exactly as under ppe_flow_attack_attach alone: who reaches which monitor,
+ *     statuses 25-28 and the row of a monitor drop, udp_accum / syn_accum, the hold arming, the port byte (entry 0 of
+ *     ppe_attack_ports' table, none: port 0), the clock (ppe_attack_clock / _tick, not batch.ts).  A packet a monitor
+ *     drops never reaches FlowHandlePacket: no lookup, no claim, no tombstone, no PortScan_Detect call, no record or
+ *     cycle stamp for its source, and it is no candidate when the detector's records run out;
+ *   - the survivors take the path of ppe_flow_portscan_attach unchanged (found / FLOW_TCP_NO_SYN_FIRST / PortScan_Detect
+ *     / 24 / ACL_DROP / FlowAdd / FLOW_NOMEM, the detector's clock and batch.ts as there);
+ *   - syncount_accum gets +1 on the packet's port only for a TCP SYN packet that ends with PPE_F_NEWFLOW: a SYN the
+ *     detector drops counts in syn_accum (the monitor saw it) and not in syncount_accum; when a later SYN of its tuple
+ *     creates the flow, the +1 goes to that later packet's port.
+ * Refused before anything is touched, with the switch on, both attached and able 1: n > ppe_flow_portscan_max() and
+ * stream tracking (PPE_ENOTSUP), n above the port-scan table's max_batch (PPE_EINVAL).  With the switch on and only one
+ * of the two attached, or the table's able 0, nothing changes: the same kernels and ppe_flow_launch_info as without it.
+ * The switch is the context's, like the attachments: ppe_flow_destroy leaves it.  Unchanged: ppe_classify_flow_host
+ * refuses monitors flow-attached, the steered multi-GPU path refuses either attachment, Decode has no monitor wiring.
+ * on > 1: PPE_EINVAL.  No synchronisation: it applies to the ppe_classify_flow calls made after it. */
+int  ppe_flow_combine(ppe_ctx_t *ctx, uint32_t on);
 
 
 /* ---- Land, SYN-flood and UDP-flood monitors on the stateless classify path (dataplane/src/attack/dp_attack.c) ----
@@ -781,7 +807,8 @@ int  ppe_attack_attach(ppe_ctx_t *ctx, ppe_attack_t *atk);        /* NULL detach
  * one that the other point holds returns PPE_EINVAL ("detach first"), as does an object of another context.
  * ppe_attack_destroy detaches from whichever point holds the object; ppe_flow_destroy leaves the attachment (it is
  * the context's, like the table pointer).  ppe_classify_flow still returns PPE_ENOTSUP, before touching anything,
- * with stream tracking on, a port-scan table attached, or an object attached with ppe_attack_attach. */
+ * with stream tracking on, a port-scan table attached, or an object attached with ppe_attack_attach.  Also PPE_ENOTSUP:
+ * a port-scan table flow-attached with able 1 at the same time, unless ppe_flow_combine is on. */
 int  ppe_flow_attack_attach(ppe_ctx_t *ctx, ppe_attack_t *atk);   /* NULL detaches */
 /* the rule file load / DP_Attack_Del_All / dp_attack_defend_time_set: the rules and hold_seconds (the state stays) */
 int  ppe_attack_set(ppe_attack_t *atk, const ppe_attack_cfg_t *cfg);

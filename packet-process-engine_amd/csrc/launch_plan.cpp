@@ -366,4 +366,13 @@ uint32_t ppe_pick_flow_portscan(uint32_t n, int flow_attached, uint32_t able) {
     return n <= PPE_FLOW_PS_MAX ? PPE_FPS_KERNEL : PPE_FPS_REFUSE;
 }
 
+// the detector and the attack monitors both flow-attached (csrc/ppe_kernels_flow_portscan_attack.hip): the reference's
+// whole path in one launch, for a context that asked for it (ppe_flow_combine; off, the batch is refused as it always
+// was); a batch the detector's kernel cannot take is refused with the monitors as without them.  fps PLAIN (no table, or
+// portscan_able == 0) or no monitors: not the combination, whatever the switch says
+uint32_t ppe_pick_flow_combined(uint32_t fps, int atk_flow_attached, uint32_t combine_on) {
+    if (fps == PPE_FPS_PLAIN || !atk_flow_attached) return PPE_FPC_NONE;
+    return (fps == PPE_FPS_KERNEL && combine_on == 1u) ? PPE_FPC_KERNEL : PPE_FPC_REFUSE;
+}
+
 }  // extern "C"

@@ -216,6 +216,7 @@ struct ppe_ctx {
     ppe_portscan_table *ps_flow = nullptr;  // ppe_flow_portscan_attach: ppe_classify_flow's detector (never the same table as ps)
     ppe_attack *atk = nullptr;         // ppe_attack_attach
     ppe_attack *atk_flow = nullptr;    // ppe_flow_attack_attach: ppe_classify_flow's monitors (never the same object as atk)
+    uint32_t flow_combine = 0;         // ppe_flow_combine: ps_flow (able 1) and atk_flow on one batch, in one launch
     FlowTable *flow = nullptr;  // ppe_flow_create
     LookupStage lk;             // ppe_acl_lookup_host
     uint32_t *d_steer = nullptr;  // ppe_steer_partition: per-tile owner counts / offsets
@@ -668,10 +669,11 @@ int ps_prepass(ppe_ctx *c, const ppe_batch_t *in, uint32_t nb, const ppe_cfg_t *
 // of batch 1, ... (no barrier between batches, one image staging for all of them).
 // small (flow-table launches only): the one-launch kernel of one 1024-thread workgroup, classify then finalize, with
 // finalize's own arguments; with fps, the one-launch kernel with the port-scan detector inside and its arguments
+// (fps_atk: the one with the flow-attached monitors in it as well)
 int launch(ppe_ctx *c, const ppe_batch_t *in, const ppe_result_t *out, uint32_t nb, const ppe_cfg_t *cfg,
            hipStream_t s, int slot_set, uint32_t idx_base = 0, const ppe_flowdev *fl = nullptr,
            uint32_t *grid_out = nullptr, uint32_t atk_pbase = 0, const ppe_flow_small_tail *small = nullptr,
-           const ppe_ps_kargs *fps = nullptr) {
+           const ppe_ps_kargs *fps = nullptr, bool fps_atk = false) {
     const int r = c->running;
     const ppe_plan &plan = c->plan[r][fl != nullptr];
     ppe_kargs a;
@@ -755,7 +757,8 @@ int launch(ppe_ctx *c, const ppe_batch_t *in, const ppe_result_t *out, uint32_t 
     }
     rc = track_launch(c, grid, a);
     if (rc != PPE_OK) return rc;
-    rc = fps     ? ppe_launch_flow_portscan(&a, small, fps, (int)plan.mode, (void *)s, (void *)e0, (void *)e1)
+    rc = fps_atk ? ppe_launch_flow_portscan_attack(&a, small, fps, (int)plan.mode, (void *)s, (void *)e0, (void *)e1)
+         : fps   ? ppe_launch_flow_portscan(&a, small, fps, (int)plan.mode, (void *)s, (void *)e0, (void *)e1)
          : small ? ppe_launch_flow_small(&a, small, (int)plan.mode, (void *)s, (void *)e0, (void *)e1)
                  : ppe_launch_classify(&a, grid, (int)plan.mode, (int)plan.pipe, (int)plan.block, fl != nullptr,
                                        (void *)s, (void *)e0, (void *)e1);
@@ -1488,6 +1491,16 @@ int ppe_flow_portscan_attach(ppe_ctx_t *c, ppe_portscan_t *t) {
 
 uint32_t ppe_flow_portscan_max(void) { return PPE_FLOW_PS_MAX; }
 
+// The context's switch for a port-scan table (able 1) and attack monitors both flow-attached: off, ppe_classify_flow
+// refuses such a batch, as it always did; on, it runs the monitors, the detector and the table in one launch
+// (ppe_pick_flow_combined).  Like the attachments it is the context's: ppe_flow_destroy leaves it
+int ppe_flow_combine(ppe_ctx_t *c, uint32_t on) {
+    if (!c) return PPE_EINVAL;
+    if (on > 1u) return fail(c, PPE_EINVAL, "ppe_flow_combine: on must be 0 or 1");
+    c->flow_combine = on;
+    return PPE_OK;
+}
+
 int ppe_portscan_clock(ppe_portscan_t *t, uint64_t now_cycles, uint64_t now_seconds) {
     if (!t) return PPE_EINVAL;
     t->now_cycles = now_cycles;  // by value into the kernel arguments of the batches enqueued from now on
@@ -2125,8 +2138,11 @@ int ppe_classify_flow(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *o
     // PPE_FLOW_PS_MAX packets; refused before anything is touched otherwise
     ppe_portscan_table *pt = c->ps_flow;
     const uint32_t fps = ppe_pick_flow_portscan(in->n, pt != nullptr, pt ? pt->cfg.able : 0u);
+    // with monitors flow-attached as well: the kernel with both inside for a context that asked for it
+    // (ppe_flow_combine), else refused
+    const uint32_t fpc = ppe_pick_flow_combined(fps, c->atk_flow != nullptr, c->flow_combine);
     if (fps != PPE_FPS_PLAIN) {
-        if (c->atk_flow)
+        if (fpc == PPE_FPC_REFUSE && !c->flow_combine)
             return fail(c, PPE_ENOTSUP, "ppe_classify_flow with a port-scan table and attack monitors both flow-attached "
                                         "is not supported");
         if (fps == PPE_FPS_REFUSE)
@@ -2187,7 +2203,7 @@ int ppe_classify_flow(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *o
         ds.upd_wgs = 0;
         const ppe_flow_small_tail tail = {in->len,      out->verdict, out->acl_hit, out->fw_idx, out->drop_idx,
                                           out->tile_cnt, out->part8,  0u,           0u};
-        rc = launch(c, in, out, 1, cfg, s, 0, 0, &ds, nullptr, 0, &tail, &pa);
+        rc = launch(c, in, out, 1, cfg, s, 0, 0, &ds, nullptr, 0, &tail, &pa, fpc == PPE_FPC_KERNEL);
         if (rc != PPE_OK) return rc;  // (nothing ran: both tables are as they were)
     } else if (small) {
         ppe_flowdev ds = d;
@@ -2241,7 +2257,7 @@ int ppe_classify_flow(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *o
             }
         }
     }
-    t.last_kind = fps == PPE_FPS_KERNEL ? 2u : small ? 1u : 0u;
+    t.last_kind = fpc == PPE_FPC_KERNEL ? 3u : fps == PPE_FPS_KERNEL ? 2u : small ? 1u : 0u;
     t.last_launches = (fps == PPE_FPS_KERNEL || small) ? 1u : 2u;
     t.cum_n[t.batches % FlowTable::kSnapRing] = t.tot_n;
     t.cum_rev[t.batches % FlowTable::kSnapRing] = t.tot_rev;

@@ -498,6 +498,12 @@ int ppe_launch_defrag_small(const void *args, uint32_t bytes, void *stream);
  * inside (1 <= n <= PPE_FLOW_PS_MAX), PPE_FPS_REFUSE a larger batch (PPE_ENOTSUP before anything is touched) */
 enum { PPE_FPS_PLAIN = 0, PPE_FPS_KERNEL = 1, PPE_FPS_REFUSE = 2 };
 uint32_t ppe_pick_flow_portscan(uint32_t n, int flow_attached, uint32_t able);
+/* the detector and the attack monitors on one flow batch.  fps: ppe_pick_flow_portscan's answer.  PPE_FPC_NONE: not the
+ * combination (fps PLAIN, or no monitors flow-attached): as before; PPE_FPC_KERNEL: the combined kernel
+ * (csrc/ppe_kernels_flow_portscan_attack.hip: fps KERNEL, monitors, combine on); PPE_FPC_REFUSE: refuse (monitors
+ * flow-attached and fps != PLAIN, with combine off or fps REFUSE) */
+enum { PPE_FPC_NONE = 0, PPE_FPC_KERNEL = 1, PPE_FPC_REFUSE = 2 };
+uint32_t ppe_pick_flow_combined(uint32_t fps, int atk_flow_attached, uint32_t combine_on);
 /* the monitors' set / tick / clear kernel (csrc/ppe_attack.hip), stream-ordered.  Returns hipError_t */
 int ppe_launch_attack_ctl(const struct ppe_atk_kargs *a, void *stream);
 /* one kernel of the port-scan pre-pass (csrc/ppe_portscan.hip), grid sized from the arguments.  Returns hipError_t */
@@ -518,6 +524,11 @@ int ppe_launch_flow_small(const struct ppe_kargs *a, const struct ppe_flow_small
  * PPE_FLOW_PS_BLOCK threads, a->batch[0].n <= PPE_FLOW_PS_MAX; a->flow.upd_wgs must be 0.  Returns hipError_t */
 int ppe_launch_flow_portscan(const struct ppe_kargs *a, const struct ppe_flow_small_tail *t,
                              const struct ppe_ps_kargs *ps, int mode, void *stream, void *ev_start, void *ev_stop);
+/* the same with the attack monitors in the classify phase and the syncount_accum count in finalize
+ * (csrc/ppe_kernels_flow_portscan_attack.hip): a->fatk_st and a->fatk_slots must be set.  Returns hipError_t */
+int ppe_launch_flow_portscan_attack(const struct ppe_kargs *a, const struct ppe_flow_small_tail *t,
+                                    const struct ppe_ps_kargs *ps, int mode, void *stream, void *ev_start,
+                                    void *ev_stop);
 #define PPE_FLOW_BLOCK 256      /* flow kernels' workgroup size */
 /* steering: 0 count, 1 scan (one workgroup), 2 scatter the permutation; rows: gather / scatter of fixed rows */
 int ppe_launch_steer(int phase, const struct ppe_steer_kargs *a, uint32_t grid, void *stream);

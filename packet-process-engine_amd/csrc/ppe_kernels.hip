@@ -2547,20 +2547,28 @@ enum { FPG_ALL = 0, FPG_CLAIM, FPG_EMIN, FPG_NCREATED, FPG_GRANTED, FPG_OCC, FPG
 constexpr uint32_t FPS_INF = 0xffffffffu;
 constexpr uint32_t FPS_NOREC = 0x20000u, FPS_STEPPED = 0x40000u;  // a source's LDS port word, beside PPE_PS_LIVE
 
-template <int MODE>
+// ATK (csrc/ppe_kernels_flow_portscan_attack.hip; the monitors flow-attached as well, ppe_flow_combine):
+// the classify phase is the FLOW + ATK body, so a packet a monitor drops leaves it final and without PPE_F_L4: not
+// pending, no claim, no candidate, and the rounds run over the survivors unchanged; finalize counts the TCP SYN creators
+// per port (ballots, one LDS add per non-empty port and wave) and adds them into words 3 port + 2 (syncount_accum) of
+// slot 0 of the monitors' slot array, the slot the classify phase of this one workgroup flushed its own counts into.
+template <int MODE, bool ATK = false>
 __global__ __launch_bounds__(PPE_FLOW_PS_BLOCK) void ppe_flow_ps_kernel(ppe_flow_ps_kargs a) {
     constexpr int BLOCK = PPE_FLOW_PS_BLOCK;
     static_assert(sizeof(ppe_flow_ps_kargs) <= 4096u, "HIP's limit for a kernel's explicit arguments");
     static_assert(offsetof(ppe_flow_ps_kargs, k) == 0u, "the classify arguments first, at ppe_kargs' own offsets");
     static_assert(PPE_FLOW_PS_MAX <= (uint32_t)BLOCK, "one packet per thread");
-    classify_body<MODE, PF_HOIST, BLOCK, true>(a.k);
+    classify_body<MODE, PF_HOIST, BLOCK, true, false, false, false, ATK>(a.k);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");
     // LDS: what the classify phase had in front of the image (key slots, bins, owner buckets), free behind the barrier
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     using L = Lds<BLOCK, true, 4u * PPE_UPD_OWNERS * (1u + (PPE_UPD_LDS ? PPE_UPD_CAP : 0u))>;
-    static_assert(4u * (PPE_NBINS + 32u + 10u * BLOCK + FPG_WORDS) <= L::IMGB, "the resolve arrays fit in front of the image");
+    // (ATK: the classify body keeps nothing more in LDS than without the monitors, whose counts live in the bins it
+    // flushed into its slot before its last barrier; syn_new[4] behind g)
+    static_assert(4u * (PPE_NBINS + 32u + 10u * BLOCK + FPG_WORDS + (ATK ? 4u : 0u)) <= L::IMGB,
+                  "the resolve arrays fit in front of the image");
     uint32_t *bins = smem, *lcnt = bins + PPE_NBINS;
     uint32_t *tmin = lcnt + 32u, *smin = tmin + BLOCK, *created = smin + BLOCK;  // by tuple / source / tuple name
     uint32_t *s_hold = created + BLOCK, *s_lc = s_hold + 2 * BLOCK;              // [2][BLOCK]: low, high words
@@ -2570,6 +2578,8 @@ __global__ __launch_bounds__(PPE_FLOW_PS_BLOCK) void ppe_flow_ps_kernel(ppe_flow
     const uint32_t n = a.k.batch[0].n, ntiles = (n + 63u) >> 6, p = tid;
     for (uint32_t i = tid; i < PPE_NBINS + 32u; i += BLOCK) bins[i] = 0;
     if (tid < FPG_WORDS) g[tid] = 0;
+    if constexpr (ATK)  // syn_new = g + FPG_WORDS: this batch's SYN-created flows per port
+        if (tid < 4u) g[FPG_WORDS + tid] = 0;
     tmin[p] = smin[p] = created[p] = FPS_INF;
     __syncthreads();
     if (tid == 0) {
@@ -2760,6 +2770,20 @@ __global__ __launch_bounds__(PPE_FLOW_PS_BLOCK) void ppe_flow_ps_kernel(ppe_flow
     }
     if (lane == 0 && ntb)
         __hip_atomic_fetch_add(&f.ctl[PPE_FCTL_TOMBS], (unsigned long long)ntb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if constexpr (ATK) {
+        // DP_Attack_SynCountMonitor in FlowAdd (flow.c:151-154): a TCP SYN packet that created its flow, on its own port
+        // (as flow_finalize_wg<BLOCK, true> counts it; a SYN the detector dropped, or one that found the flow, is none)
+        const bool syn_created = is_new && ((v >> 16) & (PPE_F_TCP | PPE_F_SYN)) == (PPE_F_TCP | PPE_F_SYN);
+        if (__builtin_amdgcn_ballot_w64(syn_created)) {  // (wave-uniform)
+            uint32_t port = 0;
+            if (syn_created && a.k.fatk_pb) port = (uint32_t)a.k.fatk_pb[p] & 3u;  // (syn_created: p < n)
+#pragma unroll
+            for (uint32_t q = 0; q < 4u; ++q) {
+                const uint32_t c = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(syn_created && port == q));
+                if (lane == 0 && c) atomicAdd(&g[FPG_WORDS + q], c);
+            }
+        }
+    }
     // the sources' records back (their owners): last_cycle, hold, the counts, the port; cycle = now for a source whose
     // detector ran (find-or-create stamps it, also for HOLD); firstinv back to 0, also for a key without a record
     if (pslot != PPE_PS_NOSLOT && srep == p) {
@@ -2797,6 +2821,10 @@ __global__ __launch_bounds__(PPE_FLOW_PS_BLOCK) void ppe_flow_ps_kernel(ppe_flow
     }
     if (tid == 128u)
         __hip_atomic_store(&f.ctl[PPE_FCTL_PS_ROUNDS], (unsigned long long)rounds, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if constexpr (ATK)  // (behind the barriers above: every wave's LDS adds are in)
+        if (tid >= 192u && tid < 196u && g[FPG_WORDS + tid - 192u])
+            __hip_atomic_fetch_add(&a.k.fatk_slots[3u * (tid - 192u) + 2u], (unsigned long long)g[FPG_WORDS + tid - 192u],
+                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 #endif
 
@@ -3125,12 +3153,22 @@ extern "C" int ppe_launch_flow_small(const ppe_kargs *a, const ppe_flow_small_ta
 #elif defined(PPE_TU_FLOW_PS)
 // csrc/ppe_kernels_flow_portscan.hip: this file again, exporting only the one-launch flow kernel with the port-scan
 // detector inside over the three image placements of the flow-table plan, at 1024 threads
-extern "C" int ppe_launch_flow_portscan(const ppe_kargs *a, const ppe_flow_small_tail *t, const ppe_ps_kargs *ps, int mode,
-                                        void *stream, void *ev_start, void *ev_stop) {
+// (csrc/ppe_kernels_flow_portscan_attack.hip, PPE_TU_FLOW_PS == 2: the same kernel with the attack monitors in its
+// classify phase and the syncount_accum count in its finalize, a->fatk_* filled)
+#if PPE_TU_FLOW_PS == 2
+#define PPE_FPS_ATK true
+extern "C" int ppe_launch_flow_portscan_attack(
+#else
+#define PPE_FPS_ATK false
+extern "C" int ppe_launch_flow_portscan(
+#endif
+    const ppe_kargs *a, const ppe_flow_small_tail *t, const ppe_ps_kargs *ps, int mode, void *stream, void *ev_start,
+    void *ev_stop) {
     const hipStream_t s = (hipStream_t)stream;
     const hipEvent_t e0 = (hipEvent_t)ev_start, e1 = (hipEvent_t)ev_stop;
     if (a->flow.upd_wgs != 0u || a->nbatch != 1u || a->ring || a->batch[0].n == 0u || a->batch[0].n > PPE_FLOW_PS_MAX)
         return (int)hipErrorInvalidValue;
+    if (PPE_FPS_ATK && (!a->fatk_st || !a->fatk_slots)) return (int)hipErrorInvalidValue;
     ppe_flow_ps_kargs k;
     k.k = *a;
     k.t = *t;
@@ -3140,9 +3178,9 @@ extern "C" int ppe_launch_flow_portscan(const ppe_kargs *a, const ppe_flow_small
     const size_t base = ppe_classify_fixed_lds(PPE_FLOW_PS_BLOCK, PF_HOIST, mode) + ppe_flow_lds_extra();
     const size_t shmem = mode == IMG_GLOBAL ? base : base + (((size_t)a->stage_words * 4u + 1023u) & ~(size_t)1023u);
     const dim3 g(1), b(PPE_FLOW_PS_BLOCK);
-    if (mode == IMG_LDS) hipExtLaunchKernelGGL(ppe_flow_ps_kernel<IMG_LDS>, g, b, shmem, s, e0, e1, 0, k);
-    else if (mode == IMG_SPLIT) hipExtLaunchKernelGGL(ppe_flow_ps_kernel<IMG_SPLIT>, g, b, shmem, s, e0, e1, 0, k);
-    else hipExtLaunchKernelGGL(ppe_flow_ps_kernel<IMG_GLOBAL>, g, b, shmem, s, e0, e1, 0, k);
+    if (mode == IMG_LDS) hipExtLaunchKernelGGL((ppe_flow_ps_kernel<IMG_LDS, PPE_FPS_ATK>), g, b, shmem, s, e0, e1, 0, k);
+    else if (mode == IMG_SPLIT) hipExtLaunchKernelGGL((ppe_flow_ps_kernel<IMG_SPLIT, PPE_FPS_ATK>), g, b, shmem, s, e0, e1, 0, k);
+    else hipExtLaunchKernelGGL((ppe_flow_ps_kernel<IMG_GLOBAL, PPE_FPS_ATK>), g, b, shmem, s, e0, e1, 0, k);
     return (int)hipGetLastError();
 }
 #elif defined(PPE_TU_STREAM)

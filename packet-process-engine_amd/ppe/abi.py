@@ -341,14 +341,14 @@ EXPORTS = [
     "ppe_format_tcpstream_stat",
     "ppe_portscan_create", "ppe_portscan_destroy", "ppe_portscan_attach", "ppe_portscan_clock", "ppe_portscan_set",
     "ppe_portscan_age", "ppe_portscan_info", "ppe_portscan_dump", "ppe_portscan_last_error", "ppe_portscan_prepass_info",
-    "ppe_flow_portscan_attach", "ppe_flow_portscan_max", "ppe_flow_portscan_rounds",
+    "ppe_flow_portscan_attach", "ppe_flow_portscan_max", "ppe_flow_portscan_rounds", "ppe_flow_combine",
     "ppe_format_pkt_stat_ps", "ppe_format_fw_config",
     "ppe_attack_create", "ppe_attack_destroy", "ppe_attack_attach", "ppe_flow_attack_attach", "ppe_attack_set", "ppe_attack_clock",
     "ppe_attack_tick", "ppe_attack_ports", "ppe_attack_info", "ppe_attack_clear_stat", "ppe_attack_last_error",
     "ppe_format_attack_stat", "ppe_format_pkt_stat_atk",
     # csrc/ppe_internal.h: the host-only launch planner (internal helpers, not part of the public headers)
     "ppe_plan_image", "ppe_pick_groups", "ppe_pick_portscan", "ppe_pick_portscan_prepass", "ppe_pick_attack", "ppe_pick_attack_flow", "ppe_pick_flow_small",
-    "ppe_pick_flow_portscan",
+    "ppe_pick_flow_portscan", "ppe_pick_flow_combined",
     # ppe_acl.h
     "ppe_rule_list_init", "ppe_rule_list_free", "Rule_add", "Rule_del_by_id", "Rule_del_all",
     "Rule_duplicate_check", "Rule_Load_Line", "ppe_rule_load_file", "DP_Acl_Rule_Init", "DP_Acl_Load_Rule",
@@ -437,6 +437,8 @@ def _open(p: Path, mode, strict: bool = True) -> C.CDLL:
         "ppe_flow_portscan_attach": ([vp, vp], C.c_int),
         "ppe_flow_portscan_max": ([], u32),
         "ppe_flow_portscan_rounds": ([vp, C.POINTER(u32)], C.c_int),
+        "ppe_flow_combine": ([vp, u32], C.c_int),
+        "ppe_pick_flow_combined": ([u32, C.c_int, u32], u32),
         "ppe_flow_age": ([vp, u64, u64, C.POINTER(u64)], C.c_int),
         "ppe_flow_info": ([vp, C.POINTER(FlowInfo)], C.c_int),
         "ppe_flow_clear_stat": ([vp], C.c_int),

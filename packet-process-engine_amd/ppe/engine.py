@@ -200,7 +200,8 @@ class Engine:
 
     def flow_launch_info(self) -> tuple:
         """ppe_flow_launch_info: (kind, launches) of the last flow batch: (1, 1) the one-launch kernel, (2, 1) the
-        one-launch kernel with the port-scan detector inside, (0, 2) the two launches, (0, 0) before the first."""
+        one-launch kernel with the port-scan detector inside, (3, 1) that kernel with the flow-attached monitors in it as
+        well (flow_combine), (0, 2) the two launches, (0, 0) before the first."""
         k, n = C.c_uint32(9), C.c_uint32(9)
         self._check(self.lib.ppe_flow_launch_info(self.ctx, C.byref(k), C.byref(n)), "ppe_flow_launch_info")
         return k.value, n.value
@@ -214,6 +215,12 @@ class Engine:
         r = C.c_uint32(0)
         self._check(self.lib.ppe_flow_portscan_rounds(self.ctx, C.byref(r)), "ppe_flow_portscan_rounds")
         return r.value
+
+    def flow_combine(self, on: int) -> None:
+        """ppe_flow_combine: 1, a flow batch with a port-scan table (able 1) and attack monitors both flow-attached runs
+        the monitors, the detector and the table in one launch (flow_launch_info (3, 1)); 0 (a new context), it is
+        refused as before.  The context's: flow_destroy leaves it."""
+        self._check(self.lib.ppe_flow_combine(self.ctx, int(on)), "ppe_flow_combine")
 
     def flow_age(self, now: int, timeout: int = 20) -> int:
         d = C.c_uint64(0)
