@@ -151,7 +151,7 @@ extern uint32_t stream_tcp_async_oneside;
  * engine.  A packet it drops (status PPE_ST_PORTSCAN_DROP) goes to the drop hook without DP_Log_Func (flow.c:216-230
  * logs nothing), with the fields the TCP / UDP decoders wrote and without PKT_HAS_FLOW / PKT_TO_SERVER.  Setting
  * portscan_able back to 0 keeps the table and its records, and the verdicts are again those without it.  The land /
- * flood monitors are not built behind Decode. */
+ * flood monitors run ahead of the flow table only (flow_attack_able below): the stateless host paths have none. */
 extern uint32_t portscan_able;
 extern uint32_t portscan_action;
 extern uint32_t portscan_exception_freq;
@@ -170,8 +170,8 @@ struct ppe_portscan_table *DP_PortScan_Table(void);
  * Start values: flow_able 0 (OFF: Decode is the stateless path, every packet its flow's first; the reference has no
  * such switch, its Decode always goes through the table), flow_item_num 100000 (MEM_POOL_FLOW_NODE_NUM), read when
  * the table is created.  With flow_able == 1 the first flush creates the context's table (flow_item_num flows) and
- * every burst goes through ppe_classify_flow_host (ppe_hip.h) in burst order, a burst larger than the first in
- * chunks; across threads the order is the order in which the flushes take the engine.  Then a packet whose flow exists
+ * every burst goes through ppe_classify_flow_host_ports (ppe_hip.h; with no monitors attached it is
+ * ppe_classify_flow_host byte for byte) in burst order, a burst larger than the first in chunks; across threads the order is the order in which the flushes take the engine.  Then a packet whose flow exists
  * is forwarded without an ACL lookup (ppe_acl_hit == -1), replies carry PKT_TO_CLIENT | PKT_HAS_FLOW, the creating
  * direction PKT_TO_SERVER | PKT_HAS_FLOW, and a packet without a flow (ACL drop, FLOW_TCP_NO_SYN_FIRST, or
  * PPE_ST_FLOW_NOMEM when the pool is empty, which goes to the drop hook without DP_Log_Func, flow.c:124-129) carries
@@ -189,11 +189,43 @@ extern uint32_t flow_item_num;
  * With flow_able == 1, flow_portscan_able == 1, portscan_able == 0 and stream tracking off, the first flush creates the
  * shim's port-scan table (the one portscan_able uses, 100,000 records) and attaches it to the flow table's path
  * (ppe_flow_portscan_attach, ppe_hip.h); every flush takes portscan_action, portscan_exception_freq, flood_hold_time and
- * DP_PortScan_Clock's values and goes through ppe_classify_flow_host.  DP_PortScan_Age and DP_PortScan_Table work on
+ * DP_PortScan_Clock's values and goes through ppe_classify_flow_host_ports.  DP_PortScan_Age and DP_PortScan_Table work on
  * that table.  A packet the detector drops (PPE_ST_PORTSCAN_DROP) goes to the drop hook without DP_Log_Func, without
  * PKT_HAS_FLOW and without a direction flag.  With flow_able == 0 it has no effect.  Setting it back to 0 detaches the
  * table and keeps its records. */
 extern uint32_t flow_portscan_able;
+/* The land, SYN-flood, SYN-count and UDP-flood monitors ahead of the flow table (DecodeIPV4 / DecodeTCP call them before
+ * FlowHandlePacket, decode-ipv4.c:141-149, decode-tcp.c:162-173; the SYN-count monitor counts in FlowAdd,
+ * flow.c:151-154), read per classify call.  Start value 0.  It has an effect only with flow_able == 1, as
+ * flow_portscan_able: the reference runs its monitors ahead of the flow table only, and the stateless host paths
+ * (flow_able == 0, with or without portscan_able) still have none.
+ * The shim keeps one monitor object (ppe_attack_*, ppe_hip.h), created on first use with all-zero rules
+ * (DP_Attack_Del_All's state) and hold_seconds = flood_hold_time.  While flow_able == 1 && flow_attack_able == 1 it is
+ * attached to the flow table's path (ppe_flow_attack_attach); otherwise it is detached and keeps its rules and state.
+ * Every flush with flow_able == 1 builds one input-port byte per mbuf from m->input_port (the kernels use port & 3; a
+ * reassembled datagram carries its chain head's) and goes through ppe_classify_flow_host_ports; flood_hold_time is read
+ * per flush, as the detector path reads it.  With flow_portscan_able == 1 as well the shim turns ppe_flow_combine on for
+ * its context and the burst runs the combined path (monitors, then the detector on the survivors' misses); the switch
+ * then stays on for ppe_compat_ctx() (with only one of the two attached it changes nothing).
+ * A packet a monitor drops (statuses 25-28) goes to the drop hook without DP_Log_Func (decode-ipv4.c:145-148 and
+ * decode-tcp.c:162-172 log nothing), without PKT_HAS_FLOW, without a direction flag and with ports 0: it never reached
+ * FlowHandlePacket.  flow_able == 1 with portscan_able == 1 or stream tracking is refused as above, whatever this is.
+ * Not built: the monitors on the stateless host paths, per-fragment counting (a reassembled datagram counts once), the
+ * /data/protection.rul parser (DP_Attack_Rule_Set in ppe_hip.h takes the parsed rules). */
+extern uint32_t flow_attack_able;
+/* The entry points below take the shim's lock, so they order with other threads' flushes. */
+/* the shim's monitor object for ppe_attack_info / ppe_format_attack_stat / ppe_attack_clear_stat (ppe_hip.h): created if
+ * a context exists (DP_Acl_Rule_Init), else NULL; NULL again after DP_Acl_Rule_Release, which destroys it before its
+ * context */
+struct ppe_attack;
+struct ppe_attack *DP_Attack_Object(void);
+/* DP_Attack_Del_All (dp_attack.c): every rule back to zero; the counts, holds and drop totals stay */
+void DP_Attack_Del_All(void);
+/* OCT_TIME_SECONDS_SINCE1970 for the bursts flushed afterwards, by value (the hold arming reads it).  Starts at 0. */
+void DP_Attack_Clock(uint64_t now_seconds);
+/* DP_Attack_Info_Update (dp_attack.c:712-748; once a second in the reference): pps = accum, accum = 0, expired holds
+ * cleared; sets the clock too.  PPE_OK without an object */
+int  DP_Attack_Tick(uint64_t now_seconds);
 /* FLOW_UPDATE_TIMESTAMP's clock (seconds) for the bursts flushed afterwards, by value.  Starts at 0; with
  * flow_able == 0 the classify calls keep now_seconds = 0. */
 void DP_Flow_Clock(uint64_t now_seconds);

@@ -44,7 +44,7 @@ extern "C" {
  * the land / SYN-flood / UDP-flood monitors (ppe_attack_*, statuses 25-28, ppe_format_attack_stat,
  * ppe_format_pkt_stat_atk), off until an object is attached; ppe_classify_host_ordered and
  * ppe_portscan_prepass_info; ppe_classify_flow_host and ppe_flow_launch_info; ppe_flow_portscan_attach, _max, _rounds;
- * ppe_flow_combine */
+ * ppe_flow_combine; ppe_classify_flow_host_ports (the monitors on host flow batches, ppe_flow_launch_info kind 4) */
 #define PPE_ABI_VERSION 8
 
 /* error codes (negative return values) */
@@ -444,10 +444,32 @@ int  ppe_classify_flow(ppe_ctx_t *ctx, const ppe_batch_t *in, const ppe_result_t
  * Flow batches submitted earlier on other streams must have completed (the internal stream does not wait for them). */
 int  ppe_classify_flow_host(ppe_ctx_t *ctx, const ppe_batch_t *in, const ppe_result_t *out, const ppe_cfg_t *cfg,
                             uint32_t chunk);
+/* ppe_classify_flow_host plus a host array of in->n input-port bytes for the flow-attached attack monitors
+ * (ppe_flow_attack_attach), which ppe_classify_flow_host refuses.  ports NULL: port 0 for every packet; the kernels use
+ * port & 3; the sticky device table of ppe_attack_ports is not read by this call.
+ *   - Nothing flow-attached (or only a port-scan table): byte for byte ppe_classify_flow_host, in outputs, counters,
+ *     table and launch kinds; ports is ignored.
+ *   - Monitors flow-attached: every chunk runs ppe_flow_attack_attach's semantics with its slice of ports; the clock is
+ *     ppe_attack_clock / _tick's value at the call (no tick inside a call).  The result is one core's run of the whole
+ *     batch in index order, whatever `chunk` is: the flow path is exactly sequential, and between two ticks a monitor's
+ *     verdict depends only on the packet and the interval's starting state.  A chunk of at most 256 packets
+ *     (PPE_FLOW_SMALL_ATK_CUTOFF, measured) runs in one launch (ppe_flow_launch_info kind 4; not under
+ *     PPE_FLOW_SMALL=0), a larger one in two (kind 0).  ppe_classify_flow itself never takes kind 4: with monitors attached and no
+ *     detector it reports (0, 2) at every size.
+ *   - Monitors and a port-scan table both flow-attached, its detector on: with ppe_flow_combine on, chunks of at most
+ *     ppe_flow_portscan_max() packets, each through the combined kernel (kind 3), batch.ts taken per chunk; with the
+ *     switch off PPE_ENOTSUP before anything is touched, as ppe_classify_flow.
+ * Every other refusal of ppe_classify_flow_host is kept (stream tracking, a stateless-attached table or object, lists
+ * or packed, max_batch below one tile).  A chunk's port bytes are copied on the same internal stream ahead of its
+ * launch; the zero-copy form applies only when ports is NULL or itself pinned and device-mapped, otherwise the staged
+ * path runs. */
+int ppe_classify_flow_host_ports(ppe_ctx_t *ctx, const ppe_batch_t *in, const ppe_result_t *out,
+                                 const ppe_cfg_t *cfg, uint32_t chunk, const uint8_t *ports);
 /* What the last flow batch of the context's table took: *kind 1 and *launches 1 (the one-launch kernel), 2 and 1 (the
  * one-launch kernel with the port-scan detector inside, ppe_flow_portscan_attach), 3 and 1 (that kernel with the
- * flow-attached attack monitors in it as well, ppe_flow_combine), or 0 and 2; 0 and 0 before the first batch.  NULL
- * arguments: PPE_EINVAL. */
+ * flow-attached attack monitors in it as well, ppe_flow_combine), 4 and 1 (the one-launch kernel with the
+ * flow-attached monitors in it: chunks of ppe_classify_flow_host_ports only), or 0 and 2; 0 and 0 before the first
+ * batch.  NULL arguments: PPE_EINVAL. */
 int  ppe_flow_launch_info(ppe_ctx_t *ctx, uint32_t *kind, uint32_t *launches);
 /* FlowAgeTimeoutCB: delete flows with now > last_seen && now - last_seen > timeout_seconds; *deleted = count
  * (may be NULL).  Synchronises. */
@@ -715,7 +737,8 @@ int  ppe_flow_portscan_rounds(ppe_ctx_t *ctx, uint32_t *rounds);
  * stream tracking (PPE_ENOTSUP), n above the port-scan table's max_batch (PPE_EINVAL).  With the switch on and only one
  * of the two attached, or the table's able 0, nothing changes: the same kernels and ppe_flow_launch_info as without it.
  * The switch is the context's, like the attachments: ppe_flow_destroy leaves it.  Unchanged: ppe_classify_flow_host
- * refuses monitors flow-attached, the steered multi-GPU path refuses either attachment, Decode has no monitor wiring.
+ * refuses monitors flow-attached (ppe_classify_flow_host_ports takes them, and with the switch on the combination), the
+ * steered multi-GPU path refuses either attachment.
  * on > 1: PPE_EINVAL.  No synchronisation: it applies to the ppe_classify_flow calls made after it. */
 int  ppe_flow_combine(ppe_ctx_t *ctx, uint32_t on);
 
@@ -827,6 +850,11 @@ int  ppe_attack_clear_stat(ppe_attack_t *atk);                      /* the four 
 const char *ppe_attack_last_error(ppe_attack_t *atk);
 /* `show attack stat` text (dp_show_attack_stat, dp_cmd.c:2394-2529) byte for byte; snprintf semantics */
 int  ppe_format_attack_stat(const ppe_attack_info_t *info, char *buf, size_t cap);
+/* The Decode shim's rule-file load (ppe_decode.h, flow_attack_able; declared here because it takes the rule type): the
+ * rules of the shim's monitor object become *cfg, except hold_seconds, which is the global flood_hold_time; the object
+ * is created if need be.  The counts, holds and drop totals stay.  Takes the shim's lock.  PPE_ENODEV without a
+ * context (DP_Acl_Rule_Init), PPE_EINVAL for NULL.  The /data/protection.rul parser is the caller's. */
+int DP_Attack_Rule_Set(const ppe_attack_cfg_t *cfg);
 
 /* `show packet statistic` / `show flow statistic` text (dp_show_pkt_stat / dp_show_flow_stat,
  * dataplane/src/common/dp_cmd.c:844-1818, 2346-2392) into buf (NUL-terminated, truncated to cap); returns the full

@@ -335,6 +335,15 @@ uint32_t ppe_pick_flow_small(uint32_t n, int small_allowed, int atk_flow_attache
     return (n >= 1u && n <= PPE_FLOW_SMALL_CUTOFF && small_allowed && !atk_flow_attached) ? 1u : 0u;
 }
 
+// the same kernel with the monitors in it (csrc/ppe_kernels_flow_small_attack.hip, launch kind 4): up to its own measured
+// cutoff, for a batch of ppe_classify_flow_host_ports with monitors flow-attached.  ppe_classify_flow's own batches
+// (ports_call 0) keep the two launches
+uint32_t ppe_pick_flow_small_attack(uint32_t n, int small_allowed, int atk_flow_attached, int ports_call) {
+    static_assert(PPE_FLOW_SMALL_ATK_CUTOFF >= 64u && PPE_FLOW_SMALL_ATK_CUTOFF % 64u == 0u &&
+                  PPE_FLOW_SMALL_ATK_CUTOFF <= PPE_FLOW_SMALL_CUTOFF, "a multiple of 64 inside the kernel's own bound");
+    return (n >= 1u && n <= PPE_FLOW_SMALL_ATK_CUTOFF && small_allowed && atk_flow_attached && ports_call) ? 1u : 0u;
+}
+
 // one launch of one workgroup for a small fragment batch (csrc/ppe_defrag_small.hip): up to `upto` fragments (the
 // table's: the measured cutoff, 0 under PPE_DEFRAG_SMALL=0, the diagnostic PPE_DEFRAG_SMALL=N's value; never past the
 // workgroup), unless the look-back failure hook is armed (one workgroup has no look-back to fail).  The one decision

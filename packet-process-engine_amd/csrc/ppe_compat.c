@@ -45,6 +45,9 @@ uint32_t flood_hold_time = 600;
 uint32_t flow_able = 0;
 /* PortScan_Detect on the flow table's misses (flow.c:215-230): off until set, with flow_able == 1 only (ppe_decode.h) */
 uint32_t flow_portscan_able = 0;
+/* The land / SYN-flood / SYN-count / UDP-flood monitors ahead of the flow table (decode-ipv4.c:141-149,
+ * decode-tcp.c:162-173, flow.c:151-154): off until set, with flow_able == 1 only (ppe_decode.h) */
+uint32_t flow_attack_able = 0;
 uint32_t flow_item_num = 100000;
 /* Defrag behind Decode (decode-ipv4.c:102-125, decode-defrag.c:449-487), read per flush.  The reference has no such
  * switch (DecodeIPV4 always hands a fragment to Defrag); this library starts with it OFF, like the ones above: Decode
@@ -92,6 +95,11 @@ static uint32_t g_df_ids = 0, g_df_cm = 0, g_df_fcb = 0, g_df_rb = 0;
 static mbuf_t **g_held = NULL;
 static uint32_t *g_held_free = NULL;
 static uint32_t g_held_cap = 0, g_held_nfree = 0;
+/* the monitors' object (created on first use with DP_Attack_Del_All's all-zero rules, destroyed with the context), the
+ * hold time its rules were last set with, and the clock DP_Attack_Clock / _Tick last gave; all under g_ctx_lock */
+static ppe_attack_t *g_atk = NULL;
+static uint32_t g_atk_hold = 0;
+static uint64_t g_atk_now = 0;
 static fw_alert fw_log_fun = NULL;
 static ppe_output_fn out_fw = NULL, out_drop = NULL, out_punt = NULL;
 
@@ -251,6 +259,8 @@ void DP_Acl_Rule_Release(void) {
     pthread_mutex_lock(&g_ctx_lock);  /* no flush, commit or lookup is using the context being destroyed */
     if (g_ps) ppe_portscan_destroy(g_ps);  /* (before its context) */
     g_ps = NULL;
+    if (g_atk) ppe_attack_destroy(g_atk);  /* (before its context: its rules and state go with it) */
+    g_atk = NULL;
     uint32_t nheld = 0;
     mbuf_t **held = defrag_reset_locked(&nheld);  /* the FCB table, and what it held for the drop hook below */
     if (g_ctx) ppe_ctx_destroy(g_ctx);  /* (its flow table with it) */
@@ -481,6 +491,10 @@ static void fill_mbuf(mbuf_t *m, uint32_t v, uint32_t fhash, int32_t hit, const 
     }
     const int tcp = m->proto == 6u;
     if (st == PPE_ST_IPV4_UNSUPPORT || st == PPE_ST_UDP_HEADER_ERR || st == PPE_ST_TCP_HEADER_ERR) return;
+    /* the UDP-flood monitor sits ahead of DecodeUDP (decode-ipv4.c:141-149): nothing of layer 4 is written.  The TCP
+     * monitors sit behind DecodeTCP's length checks (decode-tcp.c:146, 162-173): transport_header, then the return below
+     * (a monitor drop has no PPE_F_L4), so ports 0, no PKT_HAS_FLOW, no direction flag */
+    if (st == PPE_ST_ATTACK_UDPFLOOD) return;
     /* the L4 decoder's first length check passed: decode-udp.c:24, decode-tcp.c:146 */
     uint8_t *l4 = l3 + (l3[0] & 0x0fu) * 4u;
     m->transport_header = l4;
@@ -581,15 +595,97 @@ ppe_portscan_t *DP_PortScan_Table(void) {
     return t;
 }
 
+/* ---- the monitors behind Decode (ppe_decode.h) ---- */
+/* caller holds g_ctx_lock and g_ctx is set: the object on first use (all-zero rules, DP_Attack_Del_All's state), then
+ * flood_hold_time as it is now (the rules in force kept) */
+static int attack_object_locked(void) {
+    if (!g_atk) {
+        ppe_attack_cfg_t c;
+        memset(&c, 0, sizeof c);
+        c.hold_seconds = flood_hold_time;
+        int rc = ppe_attack_create(g_ctx, &c, &g_atk);
+        if (rc != PPE_OK) {
+            g_atk = NULL;
+            return rc;
+        }
+        g_atk_hold = c.hold_seconds;
+        rc = ppe_attack_clock(g_atk, g_atk_now);
+        if (rc != PPE_OK) return rc;
+    }
+    if (g_atk_hold != flood_hold_time) {  /* dp_attack_defend_time_set: read per flush, as the detector path reads it */
+        ppe_attack_info_t *fi = (ppe_attack_info_t *)malloc(sizeof *fi);
+        if (!fi) return PPE_ENOMEM;
+        int rc = ppe_attack_info(g_atk, fi);
+        if (rc == PPE_OK) {
+            fi->cfg.hold_seconds = flood_hold_time;
+            rc = ppe_attack_set(g_atk, &fi->cfg);
+        }
+        if (rc == PPE_OK) g_atk_hold = fi->cfg.hold_seconds;
+        free(fi);
+        return rc;
+    }
+    return PPE_OK;
+}
+
+ppe_attack_t *DP_Attack_Object(void) {
+    pthread_mutex_lock(&g_ctx_lock);
+    if (g_ctx && !g_atk) (void)attack_object_locked();
+    ppe_attack_t *t = g_atk;
+    pthread_mutex_unlock(&g_ctx_lock);
+    return t;
+}
+
+int DP_Attack_Rule_Set(const ppe_attack_cfg_t *cfg) {
+    if (!cfg) return PPE_EINVAL;
+    pthread_mutex_lock(&g_ctx_lock);
+    int rc = g_ctx ? attack_object_locked() : PPE_ENODEV;
+    if (rc == PPE_OK) {
+        ppe_attack_cfg_t c = *cfg;
+        c.hold_seconds = flood_hold_time;  /* (the shim's hold time is the global's, not the argument's) */
+        c.pad = 0;
+        rc = ppe_attack_set(g_atk, &c);
+        if (rc == PPE_OK) g_atk_hold = c.hold_seconds;
+    }
+    pthread_mutex_unlock(&g_ctx_lock);
+    return rc;
+}
+
+void DP_Attack_Del_All(void) {
+    ppe_attack_cfg_t c;
+    memset(&c, 0, sizeof c);
+    pthread_mutex_lock(&g_ctx_lock);
+    if (g_atk) {  /* (no object: its rules are all zero when it is created) */
+        c.hold_seconds = flood_hold_time;
+        if (ppe_attack_set(g_atk, &c) == PPE_OK) g_atk_hold = c.hold_seconds;
+    }
+    pthread_mutex_unlock(&g_ctx_lock);
+}
+
+void DP_Attack_Clock(uint64_t now_seconds) {
+    pthread_mutex_lock(&g_ctx_lock);
+    g_atk_now = now_seconds;
+    if (g_atk) (void)ppe_attack_clock(g_atk, now_seconds);
+    pthread_mutex_unlock(&g_ctx_lock);
+}
+
+int DP_Attack_Tick(uint64_t now_seconds) {
+    pthread_mutex_lock(&g_ctx_lock);
+    g_atk_now = now_seconds;
+    const int rc = g_atk ? ppe_attack_tick(g_atk, now_seconds) : PPE_OK;  /* (no object: nothing counted yet) */
+    pthread_mutex_unlock(&g_ctx_lock);
+    return rc;
+}
+
 /* Classify `n` mbufs on the GPU (serialised) and fill their parse fields; returns PPE_OK or a PPE_E* code. */
 static int classify_mbufs(mbuf_t **mb, uint32_t n) {
     uint8_t *hdr = (uint8_t *)burst_alloc((size_t)n * PPE_COMPAT_STRIDE, 16);
+    uint8_t *port = (uint8_t *)burst_alloc((size_t)n, 0);
     uint32_t *len = (uint32_t *)burst_alloc((size_t)n * 4, 0), *verdict = (uint32_t *)burst_alloc((size_t)n * 4, 0);
     uint32_t *fh = (uint32_t *)burst_alloc((size_t)n * 4, 0), *tuple = (uint32_t *)burst_alloc((size_t)n * 16, 0);
     uint64_t *ts = (uint64_t *)burst_alloc((size_t)n * 8, 0);
     int32_t *hit = (int32_t *)burst_alloc((size_t)n * 4, 0);
     int rc = PPE_ENOMEM;
-    if (hdr && len && verdict && fh && tuple && ts && hit) {
+    if (hdr && len && verdict && fh && tuple && ts && hit && port) {
         memset(hdr, 0, (size_t)n * PPE_COMPAT_STRIDE);
         for (uint32_t i = 0; i < n; i++) {
             mbuf_t *m = mb[i];
@@ -597,6 +693,7 @@ static int classify_mbufs(mbuf_t **mb, uint32_t n) {
             if (m->pkt_ptr && c) memcpy(hdr + (size_t)i * PPE_COMPAT_STRIDE, m->pkt_ptr, c);
             len[i] = m->pkt_totallen;
             ts[i] = m->timestamp;
+            port[i] = (uint8_t)m->input_port;  /* (a reassembled datagram: its chain head's, defrag_mbufs) */
         }
         ppe_batch_t b = {hdr, len, ts, n, PPE_COMPAT_STRIDE};
         ppe_result_t r;
@@ -626,10 +723,18 @@ static int classify_mbufs(mbuf_t **mb, uint32_t n) {
             const int fps_on = flow_on && flow_portscan_able == 1u;  /* (without the flow table: no effect) */
             if (g_ps) rc = ppe_portscan_attach(g_ctx, NULL);  /* the table keeps its records while off */
             if (rc == PPE_OK && g_ps && !fps_on) rc = ppe_flow_portscan_attach(g_ctx, NULL);
+            const int fatk_on = flow_on && flow_attack_able == 1u;  /* (without the flow table: no effect) */
+            if (rc == PPE_OK && g_atk && !fatk_on) rc = ppe_flow_attack_attach(g_ctx, NULL);  /* it keeps its state */
             if (rc == PPE_OK && flow_on) {  /* FlowHandlePacket: the table on first use, the burst in order through it */
                 rc = flow_prepare_locked(n);
                 if (rc == PPE_OK && fps_on) rc = portscan_prepare_locked(n, 1);  /* PortScan_Detect on its misses */
-                if (rc == PPE_OK) rc = ppe_classify_flow_host(g_ctx, &b, &r, &cfg, 0);
+                if (rc == PPE_OK && fatk_on) {  /* the monitors ahead of the table (decode-ipv4.c:141-149, decode-tcp.c:162-173) */
+                    rc = attack_object_locked();
+                    if (rc == PPE_OK) rc = ppe_flow_attack_attach(g_ctx, g_atk);
+                    /* with the detector as well the burst runs the combined path; the switch then stays on for the context */
+                    if (rc == PPE_OK && fps_on) rc = ppe_flow_combine(g_ctx, 1u);
+                }
+                if (rc == PPE_OK) rc = ppe_classify_flow_host_ports(g_ctx, &b, &r, &cfg, 0, port);
             } else if (rc == PPE_OK) {
                 rc = ppe_classify_host(g_ctx, &b, &r, &cfg, 0);
             }
@@ -639,6 +744,7 @@ static int classify_mbufs(mbuf_t **mb, uint32_t n) {
             for (uint32_t i = 0; i < n; i++) fill_mbuf(mb[i], verdict[i], fh[i], hit[i], tuple + 4 * (size_t)i, flow_on);
     }
     free(hdr);
+    free(port);
     free(len);
     free(verdict);
     free(fh);

@@ -43,6 +43,7 @@ struct HostStage {
     uint32_t *verdict = nullptr, *fhash = nullptr, *fw = nullptr, *drop = nullptr, *tcnt = nullptr,
              *tuple = nullptr;
     int32_t *hit = nullptr;
+    uint8_t *ports = nullptr;  // ppe_classify_flow_host_ports: the chunk's input-port bytes
     uint32_t cap = 0, stride = 0;
 };
 
@@ -669,11 +670,14 @@ int ps_prepass(ppe_ctx *c, const ppe_batch_t *in, uint32_t nb, const ppe_cfg_t *
 // of batch 1, ... (no barrier between batches, one image staging for all of them).
 // small (flow-table launches only): the one-launch kernel of one 1024-thread workgroup, classify then finalize, with
 // finalize's own arguments; with fps, the one-launch kernel with the port-scan detector inside and its arguments
-// (fps_atk: the one with the flow-attached monitors in it as well)
+// (fps_atk: the one with the flow-attached monitors in it as well); small_atk: the one-launch kernel of small with
+// the flow-attached monitors in it; fatk_pb_set: the flow-attached monitors read the port bytes fatk_pb (device
+// pointer or NULL) instead of the sticky table's entry 0
 int launch(ppe_ctx *c, const ppe_batch_t *in, const ppe_result_t *out, uint32_t nb, const ppe_cfg_t *cfg,
            hipStream_t s, int slot_set, uint32_t idx_base = 0, const ppe_flowdev *fl = nullptr,
            uint32_t *grid_out = nullptr, uint32_t atk_pbase = 0, const ppe_flow_small_tail *small = nullptr,
-           const ppe_ps_kargs *fps = nullptr, bool fps_atk = false) {
+           const ppe_ps_kargs *fps = nullptr, bool fps_atk = false, bool small_atk = false,
+           const uint8_t *fatk_pb = nullptr, bool fatk_pb_set = false) {
     const int r = c->running;
     const ppe_plan &plan = c->plan[r][fl != nullptr];
     ppe_kargs a;
@@ -707,7 +711,7 @@ int launch(ppe_ctx *c, const ppe_batch_t *in, const ppe_result_t *out, uint32_t 
         ppe_attack *t = c->atk_flow;
         a.fatk_st = t->d_st;
         a.fatk_slots = t->d_slots;
-        a.fatk_pb = t->h_ports.empty() ? nullptr : t->h_ports[0];
+        a.fatk_pb = fatk_pb_set ? fatk_pb : t->h_ports.empty() ? nullptr : t->h_ports[0];
         a.fatk_now = t->now;
         a.fatk_hold = t->cfg.hold_seconds;
         t->stream = s;
@@ -759,6 +763,7 @@ int launch(ppe_ctx *c, const ppe_batch_t *in, const ppe_result_t *out, uint32_t 
     if (rc != PPE_OK) return rc;
     rc = fps_atk ? ppe_launch_flow_portscan_attack(&a, small, fps, (int)plan.mode, (void *)s, (void *)e0, (void *)e1)
          : fps   ? ppe_launch_flow_portscan(&a, small, fps, (int)plan.mode, (void *)s, (void *)e0, (void *)e1)
+         : small_atk ? ppe_launch_flow_small_attack(&a, small, (int)plan.mode, (void *)s, (void *)e0, (void *)e1)
          : small ? ppe_launch_flow_small(&a, small, (int)plan.mode, (void *)s, (void *)e0, (void *)e1)
                  : ppe_launch_classify(&a, grid, (int)plan.mode, (int)plan.pipe, (int)plan.block, fl != nullptr,
                                        (void *)s, (void *)e0, (void *)e1);
@@ -910,6 +915,7 @@ int ppe_ctx_destroy(ppe_ctx_t *c) {
         (void)hipFree(h.drop);
         (void)hipFree(h.tcnt);
         (void)hipFree(h.tuple);
+        (void)hipFree(h.ports);
     }
     delete c;
     return PPE_OK;
@@ -1093,6 +1099,7 @@ static int host_stages_reserve(ppe_ctx_t *c, uint32_t chunk, uint32_t stride) {
         if (h.cap < chunk || h.stride != stride) {
             (void)hipFree(h.hdr); (void)hipFree(h.len); (void)hipFree(h.ts); (void)hipFree(h.verdict); (void)hipFree(h.fhash);
             (void)hipFree(h.hit); (void)hipFree(h.fw); (void)hipFree(h.drop); (void)hipFree(h.tcnt); (void)hipFree(h.tuple);
+            (void)hipFree(h.ports);
             h = HostStage{h.s};
             HIPCHK(c, hipMalloc(&h.hdr, (size_t)chunk * stride));
             HIPCHK(c, hipMalloc(&h.len, (size_t)chunk * 4));
@@ -1104,6 +1111,7 @@ static int host_stages_reserve(ppe_ctx_t *c, uint32_t chunk, uint32_t stride) {
             HIPCHK(c, hipMalloc(&h.drop, (size_t)chunk * 4));
             HIPCHK(c, hipMalloc(&h.tcnt, (size_t)(chunk / 64) * 4));
             HIPCHK(c, hipMalloc(&h.tuple, (size_t)chunk * 16));
+            HIPCHK(c, hipMalloc(&h.ports, (size_t)chunk));
             h.cap = chunk;
             h.stride = stride;
         }
@@ -2117,8 +2125,11 @@ int ppe_flow_create(ppe_ctx_t *c, uint32_t capacity, uint32_t max_batch) {
     return rc;
 }
 
-int ppe_classify_flow(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *out, const ppe_cfg_t *cfg,
-                      void *stream) {
+// ppe_classify_flow's body.  atk_pb: the port bytes the flow-attached monitors read (device pointer, or NULL: port 0);
+// ports_call: the batch is a chunk of ppe_classify_flow_host_ports, which alone may take the one-launch kernel with the
+// monitors in it (kind 4: ppe_classify_flow's own two launches with monitors attached are pinned by its tests)
+static int classify_flow_run(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *out, const ppe_cfg_t *cfg,
+                             void *stream, const uint8_t *atk_pb, bool ports_call) {
     if (!c || !out) return PPE_EINVAL;
     if (const int u = flow_usable(c)) return u;
     if (!out->verdict) return fail(c, PPE_EINVAL, "ppe_classify_flow needs the verdict output");
@@ -2186,6 +2197,10 @@ int ppe_classify_flow(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *o
     const bool small = fps != PPE_FPS_KERNEL &&
                        ppe_pick_flow_small(in->n, t.small_allowed && __atomic_load_n(&g_fail_post, __ATOMIC_RELAXED) == 0u,
                                            c->atk_flow != nullptr) != 0u;
+    // the same launch shape with the monitors in it, for a chunk of the ports call only
+    const bool small_atk = fps != PPE_FPS_KERNEL &&
+                           ppe_pick_flow_small_attack(in->n, t.small_allowed && __atomic_load_n(&g_fail_post, __ATOMIC_RELAXED) == 0u,
+                                                      c->atk_flow != nullptr, ports_call) != 0u;
     if (fps == PPE_FPS_KERNEL) {
         rc = ps_reserve_keys(pt, in->n);  // (may synchronise and rebuild the detector's table; nothing enqueued yet)
         if (rc != PPE_OK) return rc;
@@ -2203,20 +2218,20 @@ int ppe_classify_flow(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *o
         ds.upd_wgs = 0;
         const ppe_flow_small_tail tail = {in->len,      out->verdict, out->acl_hit, out->fw_idx, out->drop_idx,
                                           out->tile_cnt, out->part8,  0u,           0u};
-        rc = launch(c, in, out, 1, cfg, s, 0, 0, &ds, nullptr, 0, &tail, &pa, fpc == PPE_FPC_KERNEL);
+        rc = launch(c, in, out, 1, cfg, s, 0, 0, &ds, nullptr, 0, &tail, &pa, fpc == PPE_FPC_KERNEL, false, atk_pb, true);
         if (rc != PPE_OK) return rc;  // (nothing ran: both tables are as they were)
-    } else if (small) {
+    } else if (small || small_atk) {
         ppe_flowdev ds = d;
         ds.upd_wgs = 0;
         const ppe_flow_small_tail tail = {in->len,      out->verdict, out->acl_hit, out->fw_idx, out->drop_idx,
                                           out->tile_cnt, out->part8,  may_overflow ? 1u : 0u, 0u};
-        rc = launch(c, in, out, 1, cfg, s, 0, 0, &ds, nullptr, 0, &tail);
+        rc = launch(c, in, out, 1, cfg, s, 0, 0, &ds, nullptr, 0, &tail, nullptr, false, small_atk, atk_pb, true);
         if (rc != PPE_OK) return rc;  // (nothing ran: the table is as it was)
     } else {
         // 1. decode, hash, FlowFind; found flows are forwarded and their updates logged to the owners' buckets, the
         // rest get syn_check + ACL (would-be creators claim their slots)
         uint32_t cgrid = 0;
-        rc = launch(c, in, out, 1, cfg, s, 0, 0, &d, &cgrid);
+        rc = launch(c, in, out, 1, cfg, s, 0, 0, &d, &cgrid, 0, nullptr, nullptr, false, false, atk_pb, true);
         if (rc != PPE_OK) return rc;
         ppe_flow_kargs k;
         std::memset(&k, 0, sizeof k);
@@ -2236,7 +2251,7 @@ int ppe_classify_flow(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *o
         k.cslots = c->d_cslots;
         if (ppe_pick_attack_flow(1, c->atk_flow != nullptr)) {  // syncount_accum: the flows this batch's SYNs create
             k.atk_slots = c->atk_flow->d_slots;
-            k.atk_pb = c->atk_flow->h_ports.empty() ? nullptr : c->atk_flow->h_ports[0];
+            k.atk_pb = atk_pb;
         }
         // 2. the post-classify launch: finalize (grid-stride over the miss-tile list, usually short: at most one
         // workgroup per CU) and, beside it, the found flows' counters and last-seen times, one workgroup per owner
@@ -2257,8 +2272,8 @@ int ppe_classify_flow(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *o
             }
         }
     }
-    t.last_kind = fpc == PPE_FPC_KERNEL ? 3u : fps == PPE_FPS_KERNEL ? 2u : small ? 1u : 0u;
-    t.last_launches = (fps == PPE_FPS_KERNEL || small) ? 1u : 2u;
+    t.last_kind = fpc == PPE_FPC_KERNEL ? 3u : fps == PPE_FPS_KERNEL ? 2u : small_atk ? 4u : small ? 1u : 0u;
+    t.last_launches = (fps == PPE_FPS_KERNEL || small || small_atk) ? 1u : 2u;
     t.cum_n[t.batches % FlowTable::kSnapRing] = t.tot_n;
     t.cum_rev[t.batches % FlowTable::kSnapRing] = t.tot_rev;
     t.tot_n += in->n;
@@ -2269,10 +2284,21 @@ int ppe_classify_flow(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *o
     return PPE_OK;
 }
 
+int ppe_classify_flow(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *out, const ppe_cfg_t *cfg,
+                      void *stream) {
+    // the monitors' port bytes: entry 0 of ppe_attack_ports' sticky table
+    const uint8_t *pb = (c && c->atk_flow && !c->atk_flow->h_ports.empty()) ? c->atk_flow->h_ports[0] : nullptr;
+    return classify_flow_run(c, in, out, cfg, stream, pb, false);
+}
+
 // ppe_classify_flow for a host-resident batch: consecutive flow batches of at most `chunk` packets, every copy and
 // launch on c->host_cs in chunk order.  The flow path is exactly sequential, so the chunk size changes nothing.
-int ppe_classify_flow_host(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *out, const ppe_cfg_t *cfg,
-                           uint32_t chunk) {
+// ports_call (ppe_classify_flow_host_ports): monitors may be flow-attached; every chunk's slice of the host array
+// `ports` (NULL: port 0) is what they read, not the sticky table.  Between two ticks a monitor's verdict depends only on
+// the packet and the interval's starting state (§5.8), and no tick lies inside a call, so the chunks compose to one
+// core's run of the whole batch.
+static int classify_flow_host_run(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *out, const ppe_cfg_t *cfg,
+                                  uint32_t chunk, const uint8_t *ports, bool ports_call) {
     if (!c || !out) return PPE_EINVAL;
     if (const int u = flow_usable(c)) return u;
     if (!out->verdict) return fail(c, PPE_EINVAL, "ppe_classify_flow_host needs the verdict output");
@@ -2284,8 +2310,14 @@ int ppe_classify_flow_host(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result
     if (c->ps) return fail(c, PPE_ENOTSUP, "ppe_classify_flow_host with a port-scan table attached is not supported");
     if (c->atk) return fail(c, PPE_ENOTSUP, "ppe_classify_flow_host with attack monitors attached is not supported");
     // the monitors' per-batch port array does not map onto chunks (as ppe_classify_host_ordered)
-    if (c->atk_flow)
+    if (c->atk_flow && !ports_call)
         return fail(c, PPE_ENOTSUP, "ppe_classify_flow_host with attack monitors flow-attached is not supported");
+    if (!c->atk_flow) ports = nullptr;  // nothing reads them: exactly ppe_classify_flow_host
+    // both flow-attached, the detector on and ppe_flow_combine off: ppe_classify_flow's refusal, before anything is touched
+    if (ppe_pick_flow_combined(ppe_pick_flow_portscan(1u, c->ps_flow != nullptr, c->ps_flow ? c->ps_flow->cfg.able : 0u),
+                               c->atk_flow != nullptr, c->flow_combine) == PPE_FPC_REFUSE)
+        return fail(c, PPE_ENOTSUP, "ppe_classify_flow with a port-scan table and attack monitors both flow-attached "
+                                    "is not supported");
     int rc = check_batch(c, in, cfg);
     if (rc != PPE_OK || in->n == 0) return rc;
     // the detector on (a table flow-attached, portscan_able 1): chunks of at most PPE_FLOW_PS_MAX packets, each one launch
@@ -2299,6 +2331,9 @@ int ppe_classify_flow_host(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result
     HIPCHK(c, use_device(c));
     if (!c->host_cs) HIPCHK(c, hipStreamCreateWithFlags(&c->host_cs, hipStreamNonBlocking));
     const hipStream_t s = c->host_cs;
+    // the monitors' set / tick kernels ran on the stream of the latest classify call (the legacy default stream before
+    // the first); the internal stream does not wait for another one, so what was enqueued there completes first
+    if (c->atk_flow && c->atk_flow->stream != s) HIPCHK(c, hipStreamSynchronize(c->atk_flow->stream));
     // Zero-copy: every buffer pinned and device-mapped, one batch: the kernels read and write the host buffers
     if (env_int("PPE_HOST_ZEROCOPY", 1) && in->n <= bmax) {
         ppe_batch_t b = *in;
@@ -2308,8 +2343,12 @@ int ppe_classify_flow_host(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result
         uint32_t **outs[] = {&r.verdict, &r.flow_hash, (uint32_t **)&r.acl_hit, &r.tuple};
         for (uint32_t **o : outs)
             if (ok && *o) ok = (*o = (uint32_t *)mapped_host(*o)) != nullptr;
+        // (the ports call: only with no port array, or one that is itself pinned and device-mapped)
+        const uint8_t *dp = ports ? (const uint8_t *)mapped_host(ports) : nullptr;
+        if (ports && !dp) ok = false;
         if (ok) {
-            rc = ppe_classify_flow(c, &b, &r, cfg, (void *)s);
+            rc = ports_call ? classify_flow_run(c, &b, &r, cfg, (void *)s, dp, true)
+                            : ppe_classify_flow(c, &b, &r, cfg, (void *)s);
             HIPCHK(c, hipStreamSynchronize(s));
             return rc;
         }
@@ -2327,6 +2366,7 @@ int ppe_classify_flow_host(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result
         he = hipMemcpyAsync(h.hdr, in->hdr + (size_t)base * in->stride, (size_t)m * in->stride, h2d, s);
         if (he == hipSuccess) he = hipMemcpyAsync(h.len, in->len + base, (size_t)m * 4, h2d, s);
         if (he == hipSuccess && in->ts) he = hipMemcpyAsync(h.ts, in->ts + base, (size_t)m * 8, h2d, s);
+        if (he == hipSuccess && ports) he = hipMemcpyAsync(h.ports, ports + base, (size_t)m, h2d, s);
         if (he != hipSuccess) break;
         ppe_batch_t b = {h.hdr, h.len, in->ts ? h.ts : nullptr, m, in->stride};
         ppe_result_t r;
@@ -2335,7 +2375,8 @@ int ppe_classify_flow_host(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result
         r.flow_hash = out->flow_hash ? h.fhash : nullptr;
         r.acl_hit = out->acl_hit ? h.hit : nullptr;
         r.tuple = out->tuple ? h.tuple : nullptr;
-        rc = ppe_classify_flow(c, &b, &r, cfg, (void *)s);
+        rc = ports_call ? classify_flow_run(c, &b, &r, cfg, (void *)s, ports ? h.ports : nullptr, true)
+                        : ppe_classify_flow(c, &b, &r, cfg, (void *)s);
         if (rc != PPE_OK) break;
         he = hipMemcpyAsync(out->verdict + base, h.verdict, (size_t)m * 4, d2h, s);
         if (he == hipSuccess && out->flow_hash) he = hipMemcpyAsync(out->flow_hash + base, h.fhash, (size_t)m * 4, d2h, s);
@@ -2349,6 +2390,16 @@ int ppe_classify_flow_host(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result
     HIPCHK(c, he);
     HIPCHK(c, se);
     return PPE_OK;
+}
+
+int ppe_classify_flow_host(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *out, const ppe_cfg_t *cfg,
+                           uint32_t chunk) {
+    return classify_flow_host_run(c, in, out, cfg, chunk, nullptr, false);
+}
+
+int ppe_classify_flow_host_ports(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_result_t *out, const ppe_cfg_t *cfg,
+                                 uint32_t chunk, const uint8_t *ports) {
+    return classify_flow_host_run(c, in, out, cfg, chunk, ports, true);
 }
 
 int ppe_flow_launch_info(ppe_ctx_t *c, uint32_t *kind, uint32_t *launches) {

@@ -138,6 +138,13 @@ struct ppe_flow_kargs {
  * workgroup instead of two launches sized for 1M-packet batches (ppe_pick_flow_small).  A multiple of 64, at least 64,
  * at most 2,048, and never above the largest size at which tools/ab_flow_small.py's measurement supports it. */
 #define PPE_FLOW_SMALL_CUTOFF 512u
+/* the same kernel with the flow-attached monitors in it (csrc/ppe_kernels_flow_small_attack.hip, launch kind 4;
+ * ppe_pick_flow_small_attack): a multiple of 64, at most PPE_FLOW_SMALL_CUTOFF, and never above the
+ * largest size at which tools/ab_flow_host_ports.py's measurement supports it on every workload (at 384 and above a batch
+ * of nothing but new SYN flows measured 1.3-1.7 us slower than the two launches, beyond the A/A spread) */
+#ifndef PPE_FLOW_SMALL_ATK_CUTOFF  /* (a measuring build may raise it: tools/ab_flow_host_ports.py) */
+#define PPE_FLOW_SMALL_ATK_CUTOFF 256u
+#endif
 #define PPE_FLOW_SMALL_BLOCK 1024
 /* what finalize needs beside the classify arguments (ppe_flow_kargs' fields of the same names; n, unsup_fw, now, the
  * counter slots and the table come from ppe_kargs) */
@@ -480,6 +487,11 @@ uint32_t ppe_pick_attack_flow(int flow, int flow_attached);
  * (small_allowed: not created under PPE_FLOW_SMALL=0, the post-launch failure hook not armed) and no monitors are
  * flow-attached (their syncount count lives in the post kernel); else 0, the two launches */
 uint32_t ppe_pick_flow_small(uint32_t n, int small_allowed, int atk_flow_attached);
+/* 1: the flow batch of n packets takes the one-launch kernel with the monitors in it (kind 4,
+ * csrc/ppe_kernels_flow_small_attack.hip): 1 <= n <= PPE_FLOW_SMALL_ATK_CUTOFF, the table allows it (small_allowed, as
+ * above), monitors are flow-attached and the batch comes from ppe_classify_flow_host_ports (ports_call); else 0.
+ * ppe_classify_flow's own batches never take it: their two launches with monitors attached are pinned */
+uint32_t ppe_pick_flow_small_attack(uint32_t n, int small_allowed, int atk_flow_attached, int ports_call);
 /* 1: the ppe_defrag batch of n fragments takes the one-launch kernel: 1 <= n <= PPE_DEFRAG_SMALL_CUTOFF, the table
  * allows it (small_allowed: not created under PPE_DEFRAG_SMALL=0) and the admission look-back's failure hook
  * (PPE_DF_LOOK_FAIL) is not armed; else 0, the six launches */
@@ -520,6 +532,11 @@ int ppe_launch_flow(int kind, const struct ppe_flow_kargs *a, uint32_t grid, voi
  * PPE_FLOW_SMALL_BLOCK threads; a->flow.upd_wgs must be 0.  Returns hipError_t */
 int ppe_launch_flow_small(const struct ppe_kargs *a, const struct ppe_flow_small_tail *t, int mode, void *stream,
                           void *ev_start, void *ev_stop);
+/* the same with the attack monitors in the classify phase and the syncount_accum count in finalize
+ * (csrc/ppe_kernels_flow_small_attack.hip): a->fatk_st and a->fatk_slots must be set, 1 <= a->batch[0].n <=
+ * PPE_FLOW_SMALL_CUTOFF (the kernel's own bound; the planner stops at PPE_FLOW_SMALL_ATK_CUTOFF).  Returns hipError_t */
+int ppe_launch_flow_small_attack(const struct ppe_kargs *a, const struct ppe_flow_small_tail *t, int mode, void *stream,
+                                 void *ev_start, void *ev_stop);
 /* the one-launch flow kernel with the port-scan detector inside (csrc/ppe_kernels_flow_portscan.hip): one workgroup of
  * PPE_FLOW_PS_BLOCK threads, a->batch[0].n <= PPE_FLOW_PS_MAX; a->flow.upd_wgs must be 0.  Returns hipError_t */
 int ppe_launch_flow_portscan(const struct ppe_kargs *a, const struct ppe_flow_small_tail *t,

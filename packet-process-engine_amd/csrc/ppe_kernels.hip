@@ -2465,19 +2465,38 @@ __global__ __launch_bounds__(BLOCK) void ppe_flow_post_attack_kernel(ppe_flow_ka
 // arrival to ARRIVE, then reads ARRIVE >= nwg = 1 at its first poll; the REVOKED_SEQ poll is the other workgroups'
 // branch and does not exist here.  So the kernel waits on no other workgroup and has no unbounded loop (the poll is
 // bounded as it is in the post kernel, and passes at once).
-template <int MODE>
+// ATK (csrc/ppe_kernels_flow_small_attack.hip; monitors flow-attached and a batch of ppe_classify_flow_host_ports of at
+// most PPE_FLOW_SMALL_ATK_CUTOFF packets, ppe_pick_flow_small_attack): the classify phase is the
+// FLOW + ATK body, so a packet a monitor drops leaves it final and without PPE_F_L4: no lookup, no claim, no record, in
+// no miss tile, and finalize never sees it;
+// finalize is flow_finalize_wg<1024, true>, which counts the TCP SYN creators per port in the four syn_new words behind
+// room_s (tail + 4) and adds them into words 3 port + 2 (syncount_accum) of slot blockIdx.x = 0 of the monitors' slot
+// array, the slot this one workgroup's classify phase flushed its udp_accum / syn_accum counts into.  The words ATK adds:
+//   state word 0 (decisions), the rules' words   written by the set / tick kernel of an earlier launch on the stream;
+//                the classify phase's scalar loads at its start, no store in this launch;
+//   hold flag, hold-until   the classify phase's count flush, as §5.8: an agent-scope atomic load of the flag, a CAS
+//                0 -> 1 in L2, and the winner's agent-scope atomic store of now + hold; no verdict reads either before
+//                the next tick, and nothing reads them behind the fence;
+//   slot 0's count words   agent-scope atomic adds (L2) in both phases: the classify phase's udp / syn / drop totals
+//                before its last barrier, finalize's syncount_accum behind its own barriers; no load of them here, the
+//                tick kernel of a later launch folds them;
+//   port bytes   read-only in the launch: plain loads in both phases (the classify phase's decode, finalize's
+//                syn_created lanes); a stale L1 line cannot exist for a word nobody stores.
+// The arrive-and-poll pair is untouched by ATK: one workgroup, no wait on another, no new loop.
+template <int MODE, bool ATK = false>
 __global__ __launch_bounds__(PPE_FLOW_SMALL_BLOCK) void ppe_flow_small_kernel(ppe_flow_small_kargs a) {
     constexpr int BLOCK = PPE_FLOW_SMALL_BLOCK;
     static_assert(sizeof(ppe_flow_small_kargs) <= 4096u, "HIP's limit for a kernel's explicit arguments");
     static_assert(offsetof(ppe_flow_small_kargs, k) == 0u, "the classify arguments first, at ppe_kargs' own offsets");
-    classify_body<MODE, PF_HOIST, BLOCK, true>(a.k);
+    classify_body<MODE, PF_HOIST, BLOCK, true, false, false, false, ATK>(a.k);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");
     // finalize's LDS: the first words of the key slots
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     using L = Lds<BLOCK, true, 0u>;
-    static_assert(4u * (PPE_NBINS + 32u + BLOCK + 8u) <= L::KEYB, "finalize's arrays fit the key slots");
+    // (the tail's 8 words: rev_s, a pad, room_s' two, and syn_new[4] at tail + 4, which only ATK's finalize touches)
+    static_assert(4u * (PPE_NBINS + 32u + BLOCK + (1u + 1u + 2u) + 4u) <= L::KEYB, "finalize's arrays fit the key slots");
     uint32_t *bins = smem, *lcnt = bins + PPE_NBINS, *part = lcnt + 32u, *tail = part + BLOCK;
     ppe_flow_kargs f = {};
     f.f = a.k.flow;
@@ -2494,7 +2513,11 @@ __global__ __launch_bounds__(PPE_FLOW_SMALL_BLOCK) void ppe_flow_small_kernel(pp
     f.revoke = a.t.revoke;
     f.fin_wgs = 1u;
     f.cslots = a.k.cslots;
-    flow_finalize_wg<BLOCK>(f, 1u, bins, lcnt, part, tail[0], *(unsigned long long *)(tail + 2), tail + 4);
+    if constexpr (ATK) {  // (no argument of their own: the classify arguments carry them)
+        f.atk_slots = a.k.fatk_slots;
+        f.atk_pb = a.k.fatk_pb;
+    }
+    flow_finalize_wg<BLOCK, ATK>(f, 1u, bins, lcnt, part, tail[0], *(unsigned long long *)(tail + 2), tail + 4);
 }
 #endif
 
@@ -3133,11 +3156,21 @@ extern "C" int ppe_launch_flow_post_attack(const ppe_flow_kargs *a, uint32_t gri
 #elif defined(PPE_TU_FLOW_SMALL)
 // csrc/ppe_kernels_flow_small.hip: this file again, exporting only the one-launch kernel for small flow batches over
 // the three image placements of the flow-table plan, at 1024 threads
-extern "C" int ppe_launch_flow_small(const ppe_kargs *a, const ppe_flow_small_tail *t, int mode, void *stream,
-                                     void *ev_start, void *ev_stop) {
+// (csrc/ppe_kernels_flow_small_attack.hip, PPE_TU_FLOW_SMALL == 2: the same kernel with the attack monitors in its
+// classify phase and the syncount_accum count in its finalize, a->fatk_* filled)
+#if PPE_TU_FLOW_SMALL == 2
+#define PPE_FSM_ATK true
+extern "C" int ppe_launch_flow_small_attack(
+#else
+#define PPE_FSM_ATK false
+extern "C" int ppe_launch_flow_small(
+#endif
+    const ppe_kargs *a, const ppe_flow_small_tail *t, int mode, void *stream, void *ev_start, void *ev_stop) {
     const hipStream_t s = (hipStream_t)stream;
     const hipEvent_t e0 = (hipEvent_t)ev_start, e1 = (hipEvent_t)ev_stop;
     if (a->flow.upd_wgs != 0u || a->nbatch != 1u || a->ring) return (int)hipErrorInvalidValue;
+    if (PPE_FSM_ATK && (!a->fatk_st || !a->fatk_slots || a->batch[0].n == 0u || a->batch[0].n > PPE_FLOW_SMALL_CUTOFF))
+        return (int)hipErrorInvalidValue;
     ppe_flow_small_kargs k;
     k.k = *a;
     k.t = *t;
@@ -3145,9 +3178,9 @@ extern "C" int ppe_launch_flow_small(const ppe_kargs *a, const ppe_flow_small_ta
     const size_t base = ppe_classify_fixed_lds(PPE_FLOW_SMALL_BLOCK, PF_HOIST, mode) + ppe_flow_lds_extra();
     const size_t shmem = mode == IMG_GLOBAL ? base : base + (((size_t)a->stage_words * 4u + 1023u) & ~(size_t)1023u);
     const dim3 g(1), b(PPE_FLOW_SMALL_BLOCK);
-    if (mode == IMG_LDS) hipExtLaunchKernelGGL(ppe_flow_small_kernel<IMG_LDS>, g, b, shmem, s, e0, e1, 0, k);
-    else if (mode == IMG_SPLIT) hipExtLaunchKernelGGL(ppe_flow_small_kernel<IMG_SPLIT>, g, b, shmem, s, e0, e1, 0, k);
-    else hipExtLaunchKernelGGL(ppe_flow_small_kernel<IMG_GLOBAL>, g, b, shmem, s, e0, e1, 0, k);
+    if (mode == IMG_LDS) hipExtLaunchKernelGGL((ppe_flow_small_kernel<IMG_LDS, PPE_FSM_ATK>), g, b, shmem, s, e0, e1, 0, k);
+    else if (mode == IMG_SPLIT) hipExtLaunchKernelGGL((ppe_flow_small_kernel<IMG_SPLIT, PPE_FSM_ATK>), g, b, shmem, s, e0, e1, 0, k);
+    else hipExtLaunchKernelGGL((ppe_flow_small_kernel<IMG_GLOBAL, PPE_FSM_ATK>), g, b, shmem, s, e0, e1, 0, k);
     return (int)hipGetLastError();
 }
 #elif defined(PPE_TU_FLOW_PS)

@@ -329,7 +329,7 @@ EXPORTS = [
     "ppe_host_alloc", "ppe_host_free", "ppe_memcpy_h2d", "ppe_memcpy_d2h", "ppe_memset_d", "ppe_sync",
     "ppe_counters_read", "ppe_counters_clear", "ppe_timing_enable", "ppe_timing_read", "ppe_acl_image",
     "ppe_launch_info", "ppe_last_error", "ppe_acl_build_image", "ppe_acl_free_image", "ppe_set_tuning",
-    "ppe_get_tuning", "ppe_flow_create", "ppe_flow_destroy", "ppe_classify_flow", "ppe_classify_flow_host", "ppe_flow_launch_info", "ppe_flow_age", "ppe_flow_info",
+    "ppe_get_tuning", "ppe_flow_create", "ppe_flow_destroy", "ppe_classify_flow", "ppe_classify_flow_host", "ppe_classify_flow_host_ports", "ppe_flow_launch_info", "ppe_flow_age", "ppe_flow_info",
     "ppe_flow_clear_stat", "ppe_flow_dump", "ppe_format_pkt_stat", "ppe_format_flow_stat",
     "ppe_format_pkt_stat_ex", "ppe_format_flow_stat_ex",
     "ppe_steer_partition", "ppe_gather_rows", "ppe_scatter_rows",
@@ -348,7 +348,7 @@ EXPORTS = [
     "ppe_format_attack_stat", "ppe_format_pkt_stat_atk",
     # csrc/ppe_internal.h: the host-only launch planner (internal helpers, not part of the public headers)
     "ppe_plan_image", "ppe_pick_groups", "ppe_pick_portscan", "ppe_pick_portscan_prepass", "ppe_pick_attack", "ppe_pick_attack_flow", "ppe_pick_flow_small",
-    "ppe_pick_flow_portscan", "ppe_pick_flow_combined",
+    "ppe_pick_flow_portscan", "ppe_pick_flow_combined", "ppe_pick_flow_small_attack",
     # ppe_acl.h
     "ppe_rule_list_init", "ppe_rule_list_free", "Rule_add", "Rule_del_by_id", "Rule_del_all",
     "Rule_duplicate_check", "Rule_Load_Line", "ppe_rule_load_file", "DP_Acl_Rule_Init", "DP_Acl_Load_Rule",
@@ -356,6 +356,7 @@ EXPORTS = [
     # ppe_decode.h
     "ppe_set_output_hooks", "Decode", "Decode_Flush", "Decode_Set_Burst", "DP_PortScan_Clock", "DP_PortScan_Age",
     "DP_PortScan_Table", "DP_Flow_Clock", "DP_Flow_Age", "DP_Acl_Lookup_Burst", "DP_Acl_Lookup",
+    "DP_Attack_Object", "DP_Attack_Rule_Set", "DP_Attack_Del_All", "DP_Attack_Clock", "DP_Attack_Tick",
     "reg_fw_alert", "DP_Log_Func", "ppe_compat_ctx",
 ]
 EXPORTED_DATA = ["rule_list", "dp_acl_action_default", "gWstDepth", "gAvgDepth", "gChildCount", "gNumTreeNode",
@@ -431,7 +432,9 @@ def _open(p: Path, mode, strict: bool = True) -> C.CDLL:
         "ppe_flow_destroy": ([vp], C.c_int),
         "ppe_classify_flow": ([vp, C.POINTER(Batch), C.POINTER(Result), C.POINTER(Cfg), vp], C.c_int),
         "ppe_classify_flow_host": ([vp, C.POINTER(Batch), C.POINTER(Result), C.POINTER(Cfg), u32], C.c_int),
+        "ppe_classify_flow_host_ports": ([vp, C.POINTER(Batch), C.POINTER(Result), C.POINTER(Cfg), u32, vp], C.c_int),
         "ppe_flow_launch_info": ([vp, C.POINTER(u32), C.POINTER(u32)], C.c_int),
+        "ppe_pick_flow_small_attack": ([u32, C.c_int, C.c_int, C.c_int], u32),
         "ppe_pick_flow_small": ([u32, C.c_int, C.c_int], u32),
         "ppe_pick_flow_portscan": ([u32, C.c_int, u32], u32),
         "ppe_flow_portscan_attach": ([vp, vp], C.c_int),
@@ -521,6 +524,11 @@ def _open(p: Path, mode, strict: bool = True) -> C.CDLL:
         "DP_PortScan_Clock": ([u64, u64], None),
         "DP_PortScan_Age": ([u64, C.POINTER(u64)], C.c_int),
         "DP_PortScan_Table": ([], vp),
+        "DP_Attack_Object": ([], vp),
+        "DP_Attack_Rule_Set": ([vp], C.c_int),
+        "DP_Attack_Del_All": ([], None),
+        "DP_Attack_Clock": ([u64], None),
+        "DP_Attack_Tick": ([u64], C.c_int),
         "ppe_compat_ctx": ([], vp),
         "DP_Flow_Clock": ([u64], None),
         "DP_Flow_Age": ([u64, C.POINTER(u64)], C.c_int),

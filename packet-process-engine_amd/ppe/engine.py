@@ -166,12 +166,23 @@ class Engine:
         self._check(self.lib.ppe_classify_flow(self.ctx, C.byref(b), C.byref(r), C.byref(cfg or self.cfg()),
                                                s.cuda_stream), "ppe_classify_flow")
 
+    def classify_flow_host_ports(self, hdr, lens, ports=None, ts=None, cfg: abi.Cfg | None = None, chunk: int = 0,
+                                 outputs=("verdict", "flow_hash", "acl_hit", "tuple"), out: dict | None = None) -> dict:
+        """ppe_classify_flow_host_ports: classify_flow_host with one input-port byte per packet for the flow-attached
+        attack monitors (None: port 0 for every packet; the sticky attack_ports table is not read).  ports: a numpy
+        uint8 array (staged), or with `out` a torch CPU uint8 tensor (pinned: the zero-copy form may apply; pageable:
+        the staged path runs)."""
+        return self.classify_flow_host(hdr, lens, ts, cfg, chunk, outputs, out, ports=ports, _ports_call=True)
+
     def classify_flow_host(self, hdr, lens, ts=None, cfg: abi.Cfg | None = None, chunk: int = 0,
-                           outputs=("verdict", "flow_hash", "acl_hit", "tuple"), out: dict | None = None) -> dict:
+                           outputs=("verdict", "flow_hash", "acl_hit", "tuple"), out: dict | None = None,
+                           ports=None, _ports_call: bool = False) -> dict:
         """ppe_classify_flow_host: FlowHandlePacket for a host-resident batch, in chunks through one stream in order
         (one core's results whatever `chunk` is).  hdr (n, stride) uint8, lens, ts: numpy arrays (staged copies), or
         pinned torch CPU tensors together with `out` (name -> pinned tensor), which the kernels then read and write
-        directly when the batch fits the table's max_batch."""
+        directly when the batch fits the table's max_batch.  (ports: classify_flow_host_ports only.)"""
+        if ports is not None and not _ports_call:
+            raise ValueError("ports: use classify_flow_host_ports")
         if out is not None:  # caller-owned buffers (pinned torch tensors)
             ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
             n, stride = hdr.shape
@@ -194,6 +205,22 @@ class Engine:
             b = abi.Batch(hdr.ctypes.data, lens.ctypes.data, ts.ctypes.data if ts is not None else None, n, stride)
             r = abi.Result(g("verdict"), g("flow_hash"), g("acl_hit"), g("fw_idx"), g("drop_idx"), g("tile_cnt"),
                            g("tuple"), g("part8"), g("packed"))
+        if _ports_call:
+            if ports is None:
+                pp = None
+            elif hasattr(ports, "data_ptr"):
+                if ports.numel() != n:
+                    raise ValueError("ports: one byte per packet")
+                pp = ports.data_ptr()
+            else:
+                ports = np.ascontiguousarray(ports, dtype=np.uint8)  # (kept alive by this frame until the call returns)
+                if ports.size != n:
+                    raise ValueError("ports: one byte per packet")
+                pp = ports.ctypes.data
+            rc = self.lib.ppe_classify_flow_host_ports(self.ctx, C.byref(b), C.byref(r), C.byref(cfg or self.cfg()),
+                                                       int(chunk), pp)
+            self._check(rc, "ppe_classify_flow_host_ports")
+            return res
         rc = self.lib.ppe_classify_flow_host(self.ctx, C.byref(b), C.byref(r), C.byref(cfg or self.cfg()), int(chunk))
         self._check(rc, "ppe_classify_flow_host")
         return res
@@ -201,7 +228,8 @@ class Engine:
     def flow_launch_info(self) -> tuple:
         """ppe_flow_launch_info: (kind, launches) of the last flow batch: (1, 1) the one-launch kernel, (2, 1) the
         one-launch kernel with the port-scan detector inside, (3, 1) that kernel with the flow-attached monitors in it as
-        well (flow_combine), (0, 2) the two launches, (0, 0) before the first."""
+        well (flow_combine), (4, 1) the one-launch kernel with the flow-attached monitors in it (chunks of
+        classify_flow_host_ports only), (0, 2) the two launches, (0, 0) before the first."""
         k, n = C.c_uint32(9), C.c_uint32(9)
         self._check(self.lib.ppe_flow_launch_info(self.ctx, C.byref(k), C.byref(n)), "ppe_flow_launch_info")
         return k.value, n.value
