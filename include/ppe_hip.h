@@ -44,7 +44,9 @@ extern "C" {
  * the land / SYN-flood / UDP-flood monitors (ppe_attack_*, statuses 25-28, ppe_format_attack_stat,
  * ppe_format_pkt_stat_atk), off until an object is attached; ppe_classify_host_ordered and
  * ppe_portscan_prepass_info; ppe_classify_flow_host and ppe_flow_launch_info; ppe_flow_portscan_attach, _max, _rounds;
- * ppe_flow_combine; ppe_classify_flow_host_ports (the monitors on host flow batches, ppe_flow_launch_info kind 4) */
+ * ppe_flow_combine; ppe_classify_flow_host_ports (the monitors on host flow batches, ppe_flow_launch_info kind 4);
+ * the TCP session state machine on the flow path (ppe_flow_stream_attach, _max, _dump, ppe_stream_track_counters_*,
+ * ppe_format_tcpstream_stat_ex, status 29, ppe_flow_launch_info kind 5), off until attached */
 #define PPE_ABI_VERSION 8
 
 /* error codes (negative return values) */
@@ -100,7 +102,13 @@ enum ppe_status {
     PPE_ST_ATTACK_SYNFLOOD = 26,  /* SYN-flood hold or speed       STAT_ATTACK_SYNFLOOD_DROP  dp_attack.c:637-670 */
     PPE_ST_ATTACK_SYNCOUNT = 27,  /* syncount above syn_count      STAT_ATTACK_SYNCOUNT       dp_attack.c:673-685 */
     PPE_ST_ATTACK_UDPFLOOD = 28,  /* UDP-flood hold or speed       STAT_ATTACK_UDPFLOOD_DROP  dp_attack.c:582-634 */
-    PPE_ST__ALL = 29              /* every status, the monitors' included (PPE_ST__END keeps its value) */
+    PPE_ST__ALL = 29,             /* every status, the monitors' included (PPE_ST__END keeps its value) */
+    /* the TCP session machine on the flow path (ppe_flow_stream_attach): StreamTcp rejected the packet in a state other
+     * than "no session" (stream-tcp.c:3009-3140 -> STREAMTCP_ERR -> output_drop_proc, flow.c:311-320).  The packet had
+     * its flow: hash, tuple, acl_hit and every flag stay (PPE_F_FLOW, the direction, PPE_F_NEWFLOW included), and bits
+     * 10-15 of the flags carry the reason (PPE_VERDICT_STREAM_REASON).  PPE_ST__COUNT, _END and _ALL keep their values */
+    PPE_ST_STREAM_TRACK_DROP = 29,
+    PPE_ST__ALL2 = 30             /* every status, this one included */
 };
 
 enum ppe_action { PPE_ACT_FW = 0, PPE_ACT_DROP = 1, PPE_ACT_PUNT = 2 };
@@ -129,6 +137,10 @@ enum ppe_action { PPE_ACT_FW = 0, PPE_ACT_DROP = 1, PPE_ACT_PUNT = 2 };
 #define PPE_VERDICT_STATUS(v) ((v) & 0xffu)
 #define PPE_VERDICT_ACTION(v) (((v) >> 8) & 0xffu)
 #define PPE_VERDICT_FLAGS(v)  ((v) >> 16)
+/* status PPE_ST_STREAM_TRACK_DROP only: the reason, an enum ppe_stream_track_counter from 9 up (bits 10-15 of the
+ * flags, which no other path sets; zero for every other status) */
+#define PPE_F_STREAM_REASON_SHIFT 10u
+#define PPE_VERDICT_STREAM_REASON(v) (((v) >> 26) & 63u)
 
 /* ---- packed result (ppe_result_t.packed): one 8-B word per packet holding verdict, flow hash and ACL hit ----
  * bits 0-31 flow hash | 32-36 status | 37-38 action | 39-44 flags (PPE_F_VLAN .. PPE_F_FRAG, the stateless path's
@@ -324,8 +336,9 @@ int  ppe_counters_clear(ppe_ctx_t *ctx);
  * reference's defaults {1,0,0,1}; a word above 1 is PPE_EINVAL.  reasm only feeds ppe_format_tcpstream_stat.  The
  * setting travels by value with each launch: it applies to launches enqueued after the call, no synchronisation.
  * Not supported (PPE_ENOTSUP): track && midstream && !syn_check on the stateless calls (an ACK-only packet would
- * enter segment reassembly, stream-tcp.c:371-432), and ppe_classify_flow with track (later packets of a flow need the
- * session state machine, stream-tcp.c:3005-3140); the flow table stays usable. */
+ * enter segment reassembly, stream-tcp.c:371-432), and ppe_classify_flow with track unless the session state machine
+ * is attached to the flow table (ppe_flow_stream_attach, below: later packets of a flow need it, stream-tcp.c:3005-3140;
+ * with it attached reasm also selects, and must be 0); the flow table stays usable. */
 typedef struct { uint32_t track, midstream, async_oneside, reasm; } ppe_stream_tcp_cfg_t;
 int  ppe_stream_tcp_set(ppe_ctx_t *ctx, const ppe_stream_tcp_cfg_t *cfg);
 int  ppe_stream_tcp_get(ppe_ctx_t *ctx, ppe_stream_tcp_cfg_t *cfg);
@@ -469,7 +482,8 @@ int ppe_classify_flow_host_ports(ppe_ctx_t *ctx, const ppe_batch_t *in, const pp
  * one-launch kernel with the port-scan detector inside, ppe_flow_portscan_attach), 3 and 1 (that kernel with the
  * flow-attached attack monitors in it as well, ppe_flow_combine), 4 and 1 (the one-launch kernel with the
  * flow-attached monitors in it: chunks of ppe_classify_flow_host_ports only), or 0 and 2; 0 and 0 before the first
- * batch.  NULL arguments: PPE_EINVAL. */
+ * batch; 5 and 1: the one-launch kernel with the TCP session machine behind it (ppe_flow_stream_attach).  NULL
+ * arguments: PPE_EINVAL. */
 int  ppe_flow_launch_info(ppe_ctx_t *ctx, uint32_t *kind, uint32_t *launches);
 /* FlowAgeTimeoutCB: delete flows with now > last_seen && now - last_seen > timeout_seconds; *deleted = count
  * (may be NULL).  Synchronises. */
@@ -478,6 +492,83 @@ int  ppe_flow_info(ppe_ctx_t *ctx, ppe_flow_info_t *info);         /* dp_show_fl
 int  ppe_flow_clear_stat(ppe_ctx_t *ctx);                           /* dp_clear_flow_stat (dp_cmd.c:2327) */
 /* Copy up to `max` live flows to host (table order); *n = live flows.  Synchronises. */
 int  ppe_flow_dump(ppe_ctx_t *ctx, ppe_flow_entry_t *entries, uint32_t max, uint32_t *n);
+
+/* ---- StreamTcp's session state machine on the flow-table path (dataplane/src/plugin/stream-tcp/stream-tcp.c) ----
+ * The reference runs every TCP packet that has a flow through StreamTcpPacket (flow.c:311-320) and drops what it
+ * rejects.  ppe_flow_stream_attach(ctx, 1) builds that behind the flow table: one 64-B session record per flow slot,
+ * stepped in packet order.  It runs when a flow table exists, the switch is on, and ppe_stream_tcp_set holds
+ * {track 1, midstream 0, async_oneside 0, reasm 0}: the reference's defaults with segment reassembly switched off
+ * (stream_tcp_reasm_enable, dp_cmd.c:2100), under which StreamTcpReassembleHandleSegment returns OK at once
+ * (stream-tcp-reassemble.c:460-464), no packet is cached and StreamTcp is OK or ERR.  With the switch off (a new
+ * context) every call, refusal, output and counter is what it was.
+ *   Packets: every TCP packet that ends FlowHandlePacket with a flow (status PPE_ST_ACL_FW with PPE_F_FLOW: found, or
+ *   the creator).  UDP, packets without a flow and decode drops are untouched, and the flow table is exactly what the
+ *   plain path leaves: FlowAdd, FlowUpdate, last-seen and the counters come before StreamTcp (flow.c:304-311).
+ *   Order: one core running the batch in index order; sessions of different flows do not interact.
+ *   Direction: PPE_F_TOCLIENT set is PKT_IS_TOCLIENT, clear PKT_IS_TOSERVER.  payload_len, TCP_GET_SEQ / _ACK /
+ *   _WINDOW and tcpvars.ws / TCP_GET_WSCALE are read from the TCP header as the reference's macros read them.
+ *   A dropped packet keeps flow hash, tuple, acl_hit and every flag; its action becomes DROP and it moves to the drop
+ *   list / partition.  StreamTcpPacketStateNone's four reasons are statuses 20-23, every other reason is
+ *   PPE_ST_STREAM_TRACK_DROP with the reason in the flags.  ppe_counters_t counts FLOW_PROC_OK, ACL_FW and OUT_DROP.
+ *   The engine's definition where the reference leaves the value open (StreamTcpNewSession sets state and nothing
+ *   else, stream-tcp-session.c:22-33, and client.window is read at stream-tcp.c:835 before any branch wrote it): a
+ *   session record is all zero when its flow is created (a PPE_F_NEWFLOW packet zeroes its slot's record before its
+ *   step), and a found flow without a session has an all-zero record.  Attaching zeroes every record, and so does
+ *   ppe_stream_tcp_set changing track 0 -> 1 while attached: flows alive then have no session (ssn == NULL).  A
+ *   rehash moves the records with their flows.  Not kept: ra_app_base_seq, ra_raw_base_seq, last_ts, last_pkt_ts,
+ *   os_policy, the segment lists.
+ * Refused before anything is touched: attached with track 1 and any of reasm, midstream, async_oneside 1
+ * (PPE_ENOTSUP); a port-scan table or monitors flow-attached at the same time (PPE_ENOTSUP); a device batch of more
+ * than ppe_flow_stream_max() packets (PPE_ENOTSUP; ppe_classify_flow_host takes host batches of any size in chunks
+ * of at most that); a header stride under 144 B (PPE_EINVAL: neither PPE_ST_WINDOW_PUNT nor PPE_TUPLE_OPT_PAST may
+ * stand between a SYN and its window scale); attach without a flow table (PPE_EINVAL).  Attached with track 0 the
+ * context runs the plain kernels.  One launch per batch (ppe_flow_launch_info kind 5). */
+int  ppe_flow_stream_attach(ppe_ctx_t *ctx, uint32_t on);
+uint32_t ppe_flow_stream_max(void);
+#define PPE_FLOW_STREAM_MIN_STRIDE 144u
+/* a side of a session (TcpStream, stream-tcp-private.h:118-144) and a live TCP flow's key with its session record
+ * (TcpSession, :147-153; state 0 = TCP_NONE .. 11 = TCP_CLOSED) */
+typedef struct { uint32_t isn, next_seq, last_ack, next_win, window; uint16_t flags; uint8_t wscale, pad; } ppe_stream_side_t;
+typedef struct {
+    uint32_t sip, dip;
+    uint16_t sport, dport;
+    uint32_t slot;                /* device table slot (diagnostic) */
+    uint16_t flags;               /* STREAMTCP_FLAG_* */
+    uint8_t  state, pad;
+    ppe_stream_side_t client, server;
+} ppe_flow_stream_entry_t;
+/* Copy up to `max` live TCP flows with their sessions to host (table order); *n = live TCP flows.  Synchronises. */
+int  ppe_flow_stream_dump(ppe_ctx_t *ctx, ppe_flow_stream_entry_t *entries, uint32_t max, uint32_t *n);
+/* struct tcpstream_track_stat (decode-statistic.h:118-179), every field in the reference's order; the session path
+ * counts here (the stateless path keeps feeding ppe_stream_counters_t) */
+enum ppe_stream_track_counter {
+    PPE_STC_SYN_ACK_COUNT, PPE_STC_SYN_COUNT, PPE_STC_RST_COUNT, PPE_STC_RST_BUT_NO_SESSION,
+    PPE_STC_FIN_BUT_NO_SESSION, PPE_STC_MIDSTREAM_OR_ONESIDE_DISABLE, PPE_STC_MIDSTREAM_DISABLE,
+    PPE_STC_ONESIDE_DISABLE, PPE_STC_SESSION_NO_MEM, PPE_STC_FIN_INVALID_ACK, PPE_STC_FIN_OUT_OF_WINDOW,
+    PPE_STC_SESSION_PARAM_ERR, PPE_STC_WHS3_SYNACK_TOSERVER_SYN_RECV, PPE_STC_WHS3_SYNACK_SEQ_MISMATCH,
+    PPE_STC_WHS3_SYNACK_RESEND_WITH_DIFFERENT_ACK, PPE_STC_WHS3_SYN_TOCLIENT_ON_SYN_RECV,
+    PPE_STC_WHS3_SYN_RESEND_DIFF_SEQ_ON_SYN_RECV, PPE_STC_WHS3_SYNACK_IN_WRONG_DIRECTION,
+    PPE_STC_WHS3_ACK_IN_WRONG_DIR, PPE_STC_WHS3_RIGHT_SEQ_WRONG_ACK_EVASION, PPE_STC_WHS3_WRONG_SEQ_WRONG_ACK,
+    PPE_STC_WHS3_ASYNC_WRONG_SEQ, PPE_STC_WHS3_SYNACK_WITH_WRONG_ACK, PPE_STC_WHS4_WRONG_SEQ,
+    PPE_STC_WHS4_INVALID_ACK, PPE_STC_WHS4_SYNACK_WITH_WRONG_ACK, PPE_STC_WHS4_SYNACK_WITH_WRONG_SYN,
+    PPE_STC_EST_INVALID_ACK, PPE_STC_EST_PKT_BEFORE_LAST_ACK, PPE_STC_EST_PACKET_OUT_OF_WINDOW,
+    PPE_STC_EST_SYNACK_RESEND, PPE_STC_EST_SYNACK_TOSERVER, PPE_STC_EST_SYNACK_RESEND_WITH_DIFFERENT_ACK,
+    PPE_STC_EST_SYNACK_RESEND_WITH_DIFF_SEQ, PPE_STC_EST_SYN_TOCLIENT, PPE_STC_EST_SYN_RESEND_DIFF_SEQ,
+    PPE_STC_EST_SYN_RESEND, PPE_STC_PKT_RETRANSMISSION, PPE_STC_FIN2_FIN_WRONG_SEQ, PPE_STC_FIN2_INVALID_ACK,
+    PPE_STC_FIN2_ACK_WRONG_SEQ, PPE_STC_FIN1_FIN_WRONG_SEQ, PPE_STC_FIN1_INVALID_ACK, PPE_STC_FIN1_ACK_WRONG_SEQ,
+    PPE_STC_SHUTDOWN_SYN_RESEND, PPE_STC_CLOSEWAIT_FIN_OUT_OF_WINDOW, PPE_STC_CLOSING_ACK_WRONG_SEQ,
+    PPE_STC_CLOSEWAIT_INVALID_ACK, PPE_STC_CLOSING_INVALID_ACK, PPE_STC_CLOSEWAIT_PKT_BEFORE_LAST_ACK,
+    PPE_STC_CLOSEWAIT_ACK_OUT_OF_WINDOW, PPE_STC_LASTACK_ACK_WRONG_SEQ, PPE_STC_LASTACK_INVALID_ACK,
+    PPE_STC_TIMEWAIT_ACK_WRONG_SEQ, PPE_STC_TIMEWAIT_INVALID_ACK, PPE_STC_PKT_INVALID_ACK,
+    PPE_STC_PKT_BAD_WINDOW_UPDATE, PPE_STC_PKT_BROKEN_ACK, PPE_STC__COUNT /* 58 */
+};
+typedef struct { uint64_t c[64]; } ppe_stream_track_counters_t;   /* indexed by the enum above; words 58-63 zero */
+int  ppe_stream_track_counters_read(ppe_ctx_t *ctx, ppe_stream_track_counters_t *out);   /* synchronises */
+int  ppe_stream_track_counters_clear(ppe_ctx_t *ctx);
+/* `show tcpstream statistic` text (dp_show_tcpstream_stat, dp_cmd.c:174-842) from the 64-word block: every track line
+ * from its own counter, the reassembly lines 0.  Returns the length written, or -needed when cap is too small. */
+int  ppe_format_tcpstream_stat_ex(const ppe_stream_track_counters_t *c, const ppe_stream_tcp_cfg_t *cfg, char *buf,
+                                  size_t cap);
 
 /* ---- Flow-hash steering across GPUs (the stateful path shards by flow, like Octeon's PIP tag
  * steering of a flow to one core, dataplane/src/platform/oct-init.c:139-151) ----

@@ -384,4 +384,16 @@ uint32_t ppe_pick_flow_combined(uint32_t fps, int atk_flow_attached, uint32_t co
     return (fps == PPE_FPS_KERNEL && combine_on == 1u) ? PPE_FPC_KERNEL : PPE_FPC_REFUSE;
 }
 
+// the TCP session machine behind the flow table (csrc/ppe_kernels_flow_stream.hip; ppe_flow_stream_attach): it is built
+// for the one configuration in which StreamTcp is a pure verdict (midstream 0, async_oneside 0, reasm 0), one workgroup
+// per batch, and neither the detector nor the monitors on the same batch.  Sessions not attached or tracking off: the
+// plain kernels, whatever else is set
+uint32_t ppe_pick_flow_stream(uint32_t n, int attached, uint32_t track, uint32_t midstream, uint32_t async_oneside,
+                              uint32_t reasm, int ps_flow_attached, int atk_flow_attached) {
+    if (!attached || track != 1u) return PPE_FST_PLAIN;
+    if (midstream != 0u || async_oneside != 0u || reasm != 0u) return PPE_FST_REFUSE;
+    if (ps_flow_attached || atk_flow_attached) return PPE_FST_REFUSE;
+    return n <= PPE_FLOW_ST_MAX ? PPE_FST_KERNEL : PPE_FST_REFUSE;
+}
+
 }  // extern "C"

@@ -62,6 +62,7 @@ struct LookupStage {
 struct FlowArrays {
     uint32_t *keys = nullptr, *creator = nullptr;
     unsigned long long *stats = nullptr, *recs = nullptr;
+    uint32_t *sess = nullptr;  // the TCP session records, PPE_FLOW_SESS_WORDS per slot (ppe_flow_stream_attach; else NULL)
 };
 struct FlowTable {
     uint32_t capacity = 0, max_batch = 0, nslots = 0;
@@ -101,6 +102,10 @@ struct FlowTable {
     // never, the A/B switch); what the last batch took, for ppe_flow_launch_info
     bool small_allowed = true;
     uint32_t last_kind = 0, last_launches = 0;
+    // ppe_flow_stream_attach: StreamTcp's session machine behind the table (arr[].sess beside the slot arrays); the
+    // batch's tuples when the caller asks for none (the session phase reads them)
+    bool stream_on = false;
+    uint32_t *tuple_scr = nullptr;
 };
 
 }  // namespace
@@ -218,6 +223,7 @@ struct ppe_ctx {
     ppe_attack *atk = nullptr;         // ppe_attack_attach
     ppe_attack *atk_flow = nullptr;    // ppe_flow_attack_attach: ppe_classify_flow's monitors (never the same object as atk)
     uint32_t flow_combine = 0;         // ppe_flow_combine: ps_flow (able 1) and atk_flow on one batch, in one launch
+    unsigned long long *d_stc = nullptr;  // the session path's counter block (PPE_STC_WORDS), from the first attach on
     FlowTable *flow = nullptr;  // ppe_flow_create
     LookupStage lk;             // ppe_acl_lookup_host
     uint32_t *d_steer = nullptr;  // ppe_steer_partition: per-tile owner counts / offsets
@@ -672,12 +678,13 @@ int ps_prepass(ppe_ctx *c, const ppe_batch_t *in, uint32_t nb, const ppe_cfg_t *
 // finalize's own arguments; with fps, the one-launch kernel with the port-scan detector inside and its arguments
 // (fps_atk: the one with the flow-attached monitors in it as well); small_atk: the one-launch kernel of small with
 // the flow-attached monitors in it; fatk_pb_set: the flow-attached monitors read the port bytes fatk_pb (device
-// pointer or NULL) instead of the sticky table's entry 0
+// pointer or NULL) instead of the sticky table's entry 0; fst (with small): the one-launch kernel with the TCP session
+// machine behind it and its arguments
 int launch(ppe_ctx *c, const ppe_batch_t *in, const ppe_result_t *out, uint32_t nb, const ppe_cfg_t *cfg,
            hipStream_t s, int slot_set, uint32_t idx_base = 0, const ppe_flowdev *fl = nullptr,
            uint32_t *grid_out = nullptr, uint32_t atk_pbase = 0, const ppe_flow_small_tail *small = nullptr,
            const ppe_ps_kargs *fps = nullptr, bool fps_atk = false, bool small_atk = false,
-           const uint8_t *fatk_pb = nullptr, bool fatk_pb_set = false) {
+           const uint8_t *fatk_pb = nullptr, bool fatk_pb_set = false, const ppe_flow_st_args *fst = nullptr) {
     const int r = c->running;
     const ppe_plan &plan = c->plan[r][fl != nullptr];
     ppe_kargs a;
@@ -761,7 +768,8 @@ int launch(ppe_ctx *c, const ppe_batch_t *in, const ppe_result_t *out, uint32_t 
     }
     rc = track_launch(c, grid, a);
     if (rc != PPE_OK) return rc;
-    rc = fps_atk ? ppe_launch_flow_portscan_attack(&a, small, fps, (int)plan.mode, (void *)s, (void *)e0, (void *)e1)
+    rc = fst     ? ppe_launch_flow_stream(&a, small, fst, (int)plan.mode, (void *)s, (void *)e0, (void *)e1)
+         : fps_atk ? ppe_launch_flow_portscan_attack(&a, small, fps, (int)plan.mode, (void *)s, (void *)e0, (void *)e1)
          : fps   ? ppe_launch_flow_portscan(&a, small, fps, (int)plan.mode, (void *)s, (void *)e0, (void *)e1)
          : small_atk ? ppe_launch_flow_small_attack(&a, small, (int)plan.mode, (void *)s, (void *)e0, (void *)e1)
          : small ? ppe_launch_flow_small(&a, small, (int)plan.mode, (void *)s, (void *)e0, (void *)e1)
@@ -805,6 +813,8 @@ int check_batch(ppe_ctx *c, const ppe_batch_t *in, const ppe_cfg_t *cfg) {
 }  // namespace
 
 extern "C" {
+
+static int flow_stream_zero(ppe_ctx *c);  // (with the flow table, below)
 
 int ppe_abi_version(void) { return PPE_ABI_VERSION; }
 
@@ -880,6 +890,7 @@ int ppe_ctx_destroy(ppe_ctx_t *c) {
     }
     if (c->d_cslots) (void)hipFree(c->d_cslots);
     if (c->d_sslots) (void)hipFree(c->d_sslots);
+    if (c->d_stc) (void)hipFree(c->d_stc);
     for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
     for (int i = 0; i < 2; ++i) {
         if (c->d_ring[i]) (void)hipFree(c->d_ring[i]);
@@ -1377,6 +1388,11 @@ int ppe_stream_tcp_set(ppe_ctx_t *c, const ppe_stream_tcp_cfg_t *cfg) {
     const ppe_stream_tcp_cfg_t v = cfg ? *cfg : ref;
     if (v.track > 1 || v.midstream > 1 || v.async_oneside > 1 || v.reasm > 1)
         return fail(c, PPE_EINVAL, "ppe_stream_tcp_set: every word must be 0/1");
+    // sessions attached and tracking goes on: flows alive now have no session (ssn == NULL), every record zero
+    if (c->flow && c->flow->stream_on && !c->stcp.track && v.track) {
+        const int rc = flow_stream_zero(c);
+        if (rc != PPE_OK) return rc;
+    }
     c->stcp = v;  // by value into the kernel arguments of later launches
     return PPE_OK;
 }
@@ -1906,6 +1922,7 @@ static void flow_free_arrays(FlowArrays &a) {
     (void)hipFree(a.creator);
     (void)hipFree(a.stats);
     (void)hipFree(a.recs);
+    (void)hipFree(a.sess);
     a = FlowArrays();
 }
 
@@ -1924,6 +1941,20 @@ static int flow_clear_arrays(ppe_ctx *c, FlowArrays &a, uint32_t nslots, hipStre
     HIPCHK(c, hipMemsetAsync(a.recs, 0, (size_t)nslots * 8u * PPE_FLOW_REC_WORDS, s));
     HIPCHK(c, hipMemsetAsync(a.creator, 0xff, (size_t)nslots * 4u, s));
     HIPCHK(c, hipMemsetAsync(a.stats, 0, (size_t)nslots * 32u, s));
+    if (c->flow && c->flow->stream_on) {  // the session records beside them, every one zero
+        if (!a.sess && hipMalloc(&a.sess, (size_t)nslots * 4u * PPE_FLOW_SESS_WORDS) != hipSuccess)
+            return fail(c, PPE_ENOMEM, "flow table: out of device memory (%u session records)", nslots);
+        HIPCHK(c, hipMemsetAsync(a.sess, 0, (size_t)nslots * 4u * PPE_FLOW_SESS_WORDS, s));
+    }
+    return PPE_OK;
+}
+
+// every session record of the slot arrays in use back to zero (synchronises: batches in flight finish first)
+static int flow_stream_zero(ppe_ctx *c) {
+    FlowTable &t = *c->flow;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipDeviceSynchronize());
+    if (t.arr[t.cur].sess) HIPCHK(c, hipMemset(t.arr[t.cur].sess, 0, (size_t)t.nslots * 4u * PPE_FLOW_SESS_WORDS));
     return PPE_OK;
 }
 
@@ -2010,6 +2041,18 @@ static int flow_maybe_rehash(ppe_ctx *c) {
     k.nslots = t.nslots;
     rc = ppe_launch_flow(PPE_FLOW_K_REHASH, &k, flow_grid(c, t.nslots, 256u), nullptr);
     if (rc != 0) return fail(c, PPE_EIO, "flow rehash launch failed: %s", hipGetErrorString((hipError_t)rc));
+    if (t.stream_on) {  // the session records follow their flows: a pass of its own behind the rehash launch
+        ppe_flow_st_rehash_kargs sk;
+        std::memset(&sk, 0, sizeof sk);
+        sk.src_keys = t.arr[t.cur].keys;
+        sk.dst_keys = t.arr[dst].keys;
+        sk.src_sess = t.arr[t.cur].sess;
+        sk.dst_sess = t.arr[dst].sess;
+        sk.nslots = t.nslots;
+        sk.dst_gmask = t.nslots / PPE_FLOW_GROUP - 1u;
+        rc = ppe_launch_flow_stream_rehash(&sk, flow_grid(c, t.nslots, 256u), nullptr);
+        if (rc != 0) return fail(c, PPE_EIO, "flow session rehash launch failed: %s", hipGetErrorString((hipError_t)rc));
+    }
     HIPCHK(c, hipMemset(t.ctl + PPE_FCTL_TOMBS, 0, 8u));
     HIPCHK(c, hipDeviceSynchronize());
     t.cur = dst;
@@ -2054,6 +2097,7 @@ int ppe_flow_destroy(ppe_ctx_t *c) {
     (void)hipFree(t->tile_new);
     (void)hipFree(t->upd);
     (void)hipFree(t->ucnt);
+    (void)hipFree(t->tuple_scr);
     delete t;
     c->flow = nullptr;
     return PPE_OK;
@@ -2125,6 +2169,23 @@ int ppe_flow_create(ppe_ctx_t *c, uint32_t capacity, uint32_t max_batch) {
     return rc;
 }
 
+// how a flow batch of n packets runs with respect to the TCP session machine (ppe_pick_flow_stream over the context)
+static uint32_t flow_stream_pick(const ppe_ctx *c, uint32_t n) {
+    return ppe_pick_flow_stream(n, c->flow && c->flow->stream_on, c->stcp.track, c->stcp.midstream, c->stcp.async_oneside,
+                                c->stcp.reasm, c->ps_flow != nullptr, c->atk_flow != nullptr);
+}
+// PPE_FST_REFUSE's error, by its cause
+static int flow_stream_refuse(ppe_ctx *c) {
+    if (c->stcp.midstream || c->stcp.async_oneside || c->stcp.reasm)
+        return fail(c, PPE_ENOTSUP, "TCP sessions on the flow path are built for midstream 0, async_oneside 0, reasm 0 "
+                                    "(ppe_stream_tcp_set)");
+    if (c->ps_flow || c->atk_flow)
+        return fail(c, PPE_ENOTSUP, "TCP sessions on the flow path with a port-scan table or attack monitors flow-attached "
+                                    "are not supported");
+    return fail(c, PPE_ENOTSUP, "ppe_classify_flow with TCP sessions takes at most %u packets per batch "
+                                "(ppe_flow_stream_max; ppe_classify_flow_host chunks larger ones)", PPE_FLOW_ST_MAX);
+}
+
 // ppe_classify_flow's body.  atk_pb: the port bytes the flow-attached monitors read (device pointer, or NULL: port 0);
 // ports_call: the batch is a chunk of ppe_classify_flow_host_ports, which alone may take the one-launch kernel with the
 // monitors in it (kind 4: ppe_classify_flow's own two launches with monitors attached are pinned by its tests)
@@ -2133,8 +2194,12 @@ static int classify_flow_run(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_resu
     if (!c || !out) return PPE_EINVAL;
     if (const int u = flow_usable(c)) return u;
     if (!out->verdict) return fail(c, PPE_EINVAL, "ppe_classify_flow needs the verdict output");
-    // later packets of a tracked flow need the TCP session state machine (stream-tcp.c:3005-3140): not built
-    if (c->stcp.track) return fail(c, PPE_ENOTSUP, "ppe_classify_flow with stream tracking on is not supported");
+    // later packets of a tracked flow need the TCP session state machine (stream-tcp.c:3005-3140): that takes
+    // ppe_flow_stream_attach, in the one configuration it is built for; refused before anything is touched otherwise
+    const uint32_t fst = flow_stream_pick(c, in ? in->n : 0u);
+    if (c->stcp.track && fst == PPE_FST_PLAIN)
+        return fail(c, PPE_ENOTSUP, "ppe_classify_flow with stream tracking on is not supported");
+    if (fst == PPE_FST_REFUSE) return flow_stream_refuse(c);
     // PortScan_Detect runs on flow misses only (flow.c:196-215): a table attached for the stateless path would see every
     // packet; the flow path's detector takes ppe_flow_portscan_attach
     if (c->ps) return fail(c, PPE_ENOTSUP, "ppe_classify_flow with a port-scan table attached is not supported");
@@ -2145,6 +2210,11 @@ static int classify_flow_run(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_resu
     if (rc != PPE_OK || in->n == 0) return rc;
     FlowTable &t = *c->flow;
     if (in->n > t.max_batch) return fail(c, PPE_EINVAL, "batch larger than the flow table's max_batch");
+    // a SYN's window scale must lie inside the header window: neither PPE_ST_WINDOW_PUNT nor PPE_TUPLE_OPT_PAST between
+    // a SYN and its option (Ethernet + VLAN + 60 + 60 B)
+    if (fst == PPE_FST_KERNEL && in->stride < PPE_FLOW_STREAM_MIN_STRIDE)
+        return fail(c, PPE_EINVAL, "ppe_classify_flow with TCP sessions needs a header stride of at least %u B",
+                    PPE_FLOW_STREAM_MIN_STRIDE);
     // the detector on flow misses (a table flow-attached, portscan_able 1): one launch of one workgroup, up to
     // PPE_FLOW_PS_MAX packets; refused before anything is touched otherwise
     ppe_portscan_table *pt = c->ps_flow;
@@ -2201,7 +2271,16 @@ static int classify_flow_run(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_resu
     const bool small_atk = fps != PPE_FPS_KERNEL &&
                            ppe_pick_flow_small_attack(in->n, t.small_allowed && __atomic_load_n(&g_fail_post, __ATOMIC_RELAXED) == 0u,
                                                       c->atk_flow != nullptr, ports_call) != 0u;
-    if (fps == PPE_FPS_KERNEL) {
+    if (fst == PPE_FST_KERNEL) {
+        // FlowHandlePacket, then StreamTcp for the TCP packets that have a flow: one launch of one workgroup
+        ppe_flowdev ds = d;
+        ds.upd_wgs = 0;
+        const ppe_flow_small_tail tail = {in->len,      out->verdict, out->acl_hit, out->fw_idx, out->drop_idx,
+                                          out->tile_cnt, out->part8,  may_overflow ? 1u : 0u, 0u};
+        const ppe_flow_st_args sa = {t.arr[t.cur].sess, c->d_stc, t.tuple_scr};
+        rc = launch(c, in, out, 1, cfg, s, 0, 0, &ds, nullptr, 0, &tail, nullptr, false, false, atk_pb, true, &sa);
+        if (rc != PPE_OK) return rc;  // (nothing ran: the table is as it was)
+    } else if (fps == PPE_FPS_KERNEL) {
         rc = ps_reserve_keys(pt, in->n);  // (may synchronise and rebuild the detector's table; nothing enqueued yet)
         if (rc != PPE_OK) return rc;
         ppe_ps_kargs pa;
@@ -2272,8 +2351,9 @@ static int classify_flow_run(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_resu
             }
         }
     }
-    t.last_kind = fpc == PPE_FPC_KERNEL ? 3u : fps == PPE_FPS_KERNEL ? 2u : small_atk ? 4u : small ? 1u : 0u;
-    t.last_launches = (fps == PPE_FPS_KERNEL || small || small_atk) ? 1u : 2u;
+    t.last_kind = fst == PPE_FST_KERNEL ? 5u : fpc == PPE_FPC_KERNEL ? 3u : fps == PPE_FPS_KERNEL ? 2u : small_atk ? 4u
+                  : small ? 1u : 0u;
+    t.last_launches = (fst == PPE_FST_KERNEL || fps == PPE_FPS_KERNEL || small || small_atk) ? 1u : 2u;
     t.cum_n[t.batches % FlowTable::kSnapRing] = t.tot_n;
     t.cum_rev[t.batches % FlowTable::kSnapRing] = t.tot_rev;
     t.tot_n += in->n;
@@ -2306,7 +2386,10 @@ static int classify_flow_host_run(ppe_ctx_t *c, const ppe_batch_t *in, const ppe
     if (out->fw_idx || out->drop_idx || out->tile_cnt || out->part8 || out->packed)
         return fail(c, PPE_EINVAL, "ppe_classify_flow_host takes the per-packet outputs only (no lists, no packed)");
     // ppe_classify_flow's refusals, before anything is touched
-    if (c->stcp.track) return fail(c, PPE_ENOTSUP, "ppe_classify_flow_host with stream tracking on is not supported");
+    const uint32_t fst = flow_stream_pick(c, 1u);  // (sessions attached and tracking on: every chunk is a session batch)
+    if (c->stcp.track && fst == PPE_FST_PLAIN)
+        return fail(c, PPE_ENOTSUP, "ppe_classify_flow_host with stream tracking on is not supported");
+    if (fst == PPE_FST_REFUSE) return flow_stream_refuse(c);
     if (c->ps) return fail(c, PPE_ENOTSUP, "ppe_classify_flow_host with a port-scan table attached is not supported");
     if (c->atk) return fail(c, PPE_ENOTSUP, "ppe_classify_flow_host with attack monitors attached is not supported");
     // the monitors' per-batch port array does not map onto chunks (as ppe_classify_host_ordered)
@@ -2322,8 +2405,13 @@ static int classify_flow_host_run(ppe_ctx_t *c, const ppe_batch_t *in, const ppe
     if (rc != PPE_OK || in->n == 0) return rc;
     // the detector on (a table flow-attached, portscan_able 1): chunks of at most PPE_FLOW_PS_MAX packets, each one launch
     const bool fps = ppe_pick_flow_portscan(1u, c->ps_flow != nullptr, c->ps_flow ? c->ps_flow->cfg.able : 0u) != PPE_FPS_PLAIN;
-    const uint32_t bmax = fps ? std::min(c->flow->max_batch, std::min(c->ps_flow->cfg.max_batch, PPE_FLOW_PS_MAX))
-                              : c->flow->max_batch;
+    // session batches: chunks of at most PPE_FLOW_ST_MAX packets, each one launch
+    if (fst == PPE_FST_KERNEL && in->stride < PPE_FLOW_STREAM_MIN_STRIDE)
+        return fail(c, PPE_EINVAL, "ppe_classify_flow_host with TCP sessions needs a header stride of at least %u B",
+                    PPE_FLOW_STREAM_MIN_STRIDE);
+    const uint32_t bmax = fst == PPE_FST_KERNEL ? std::min(c->flow->max_batch, PPE_FLOW_ST_MAX)
+                          : fps ? std::min(c->flow->max_batch, std::min(c->ps_flow->cfg.max_batch, PPE_FLOW_PS_MAX))
+                                : c->flow->max_batch;
     const uint32_t cmax = bmax & ~63u;
     if (cmax < 64u)
         return fail(c, PPE_EINVAL, "ppe_classify_flow_host: the %s table's max_batch is below one tile",
@@ -2513,6 +2601,105 @@ int ppe_flow_dump(ppe_ctx_t *c, ppe_flow_entry_t *entries, uint32_t max, uint32_
         ++k;
     }
     *n = k;
+    return PPE_OK;
+}
+
+// ---- StreamTcp's session machine behind the flow table (csrc/ppe_kernels_flow_stream.hip) ----
+uint32_t ppe_flow_stream_max(void) { return PPE_FLOW_ST_MAX; }
+
+int ppe_flow_stream_attach(ppe_ctx_t *c, uint32_t on) {
+    if (!c) return PPE_EINVAL;
+    if (on > 1u) return fail(c, PPE_EINVAL, "ppe_flow_stream_attach: on must be 0/1");
+    if (const int u = flow_usable(c)) return u;
+    FlowTable &t = *c->flow;
+    if (!on) {  // (the records stay allocated until ppe_flow_destroy; the next attach zeroes them)
+        t.stream_on = false;
+        return PPE_OK;
+    }
+    HIPCHK(c, use_device(c));
+    HIPCHK(c, hipDeviceSynchronize());
+    FlowArrays &a = t.arr[t.cur];
+    if (!a.sess && hipMalloc(&a.sess, (size_t)t.nslots * 4u * PPE_FLOW_SESS_WORDS) != hipSuccess)
+        return fail(c, PPE_ENOMEM, "ppe_flow_stream_attach: out of device memory (%u session records)", t.nslots);
+    if (!t.tuple_scr && hipMalloc(&t.tuple_scr, (size_t)PPE_FLOW_ST_MAX * 16u) != hipSuccess)
+        return fail(c, PPE_ENOMEM, "ppe_flow_stream_attach: out of device memory");
+    if (!c->d_stc) {
+        if (hipMalloc(&c->d_stc, PPE_STC_WORDS * 8u) != hipSuccess)
+            return fail(c, PPE_ENOMEM, "ppe_flow_stream_attach: out of device memory");
+        HIPCHK(c, hipMemset(c->d_stc, 0, PPE_STC_WORDS * 8u));
+    }
+    // attaching zeroes every record: flows alive now have no session (ssn == NULL in the reference)
+    HIPCHK(c, hipMemset(a.sess, 0, (size_t)t.nslots * 4u * PPE_FLOW_SESS_WORDS));
+    HIPCHK(c, hipDeviceSynchronize());
+    t.stream_on = true;
+    return PPE_OK;
+}
+
+int ppe_flow_stream_dump(ppe_ctx_t *c, ppe_flow_stream_entry_t *entries, uint32_t max, uint32_t *n) {
+    if (!c || !n) return PPE_EINVAL;
+    if (const int u = flow_usable(c)) return u;
+    const FlowTable &t = *c->flow;
+    const FlowArrays &a = t.arr[t.cur];
+    if (!t.stream_on || !a.sess) return fail(c, PPE_EINVAL, "ppe_flow_stream_dump: no sessions attached (ppe_flow_stream_attach)");
+    HIPCHK(c, use_device(c));
+    HIPCHK(c, hipDeviceSynchronize());
+    constexpr uint32_t W = PPE_FLOW_SLOT_WORDS, S = PPE_FLOW_SESS_WORDS;
+    std::vector<uint32_t> keys((size_t)t.nslots * W), sess;
+    HIPCHK(c, hipMemcpy(keys.data(), a.keys, keys.size() * 4u, hipMemcpyDeviceToHost));
+    if (entries && max) {
+        sess.resize((size_t)t.nslots * S);
+        HIPCHK(c, hipMemcpy(sess.data(), a.sess, sess.size() * 4u, hipMemcpyDeviceToHost));
+    }
+    uint32_t k = 0;
+    for (uint32_t s = 0; s < t.nslots; ++s) {
+        const uint32_t *kw = &keys[(size_t)W * s];
+        if (kw[3] != PPE_FS_LIVE(6u)) continue;
+        if (entries && k < max) {
+            ppe_flow_stream_entry_t &e = entries[k];
+            std::memset(&e, 0, sizeof e);
+            const uint32_t *w = &sess[(size_t)S * s];
+            e.sip = kw[0];
+            e.dip = kw[1];
+            e.sport = (uint16_t)(kw[2] & 0xffffu);
+            e.dport = (uint16_t)(kw[2] >> 16);
+            e.slot = s;
+            e.state = (uint8_t)(w[0] & 0xffu);
+            e.flags = (uint16_t)(w[0] >> 8);
+            ppe_stream_side_t *side[2] = {&e.client, &e.server};
+            for (int i = 0; i < 2; ++i) {
+                const uint32_t *q = w + 1 + 6 * i;
+                side[i]->flags = (uint16_t)(q[0] & 0xffffu);
+                side[i]->wscale = (uint8_t)(q[0] >> 16);
+                side[i]->isn = q[1];
+                side[i]->next_seq = q[2];
+                side[i]->last_ack = q[3];
+                side[i]->next_win = q[4];
+                side[i]->window = q[5];
+            }
+        }
+        ++k;
+    }
+    *n = k;
+    return PPE_OK;
+}
+
+int ppe_stream_track_counters_read(ppe_ctx_t *c, ppe_stream_track_counters_t *out) {
+    if (!c || !out) return PPE_EINVAL;
+    static_assert(sizeof(ppe_stream_track_counters_t) == PPE_STC_WORDS * 8u, "the counter block");
+    std::memset(out, 0, sizeof *out);
+    if (!c->d_stc) return PPE_OK;  // (never attached: nothing counted)
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipDeviceSynchronize());
+    HIPCHK(c, hipMemcpy(out->c, c->d_stc, PPE_STC_WORDS * 8u, hipMemcpyDeviceToHost));
+    return PPE_OK;
+}
+
+int ppe_stream_track_counters_clear(ppe_ctx_t *c) {
+    if (!c) return PPE_EINVAL;
+    if (!c->d_stc) return PPE_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipDeviceSynchronize());
+    HIPCHK(c, hipMemset(c->d_stc, 0, PPE_STC_WORDS * 8u));
     return PPE_OK;
 }
 

@@ -380,6 +380,39 @@ struct ppe_flow_ps_kargs {
     struct ppe_ps_kargs ps;
 };
 
+/* ---- the flow-table kernel with the TCP session machine behind it (csrc/ppe_kernels_flow_stream.hip) ----
+ * A flow batch of 1 <= n <= PPE_FLOW_ST_MAX packets of a context with sessions attached (ppe_flow_stream_attach) and
+ * tracking on: classify, finalize, the session walk and the final verdicts in one launch of one PPE_FLOW_ST_BLOCK-thread
+ * workgroup, one packet per thread.  The larger of 512 and 1,024 whose LDS (24.3 KB of sort keys, packet words and
+ * counters in front of every image placement) and registers fit (DESIGN.md §5.15 has the numbers). */
+#define PPE_FLOW_ST_MAX 1024u
+#define PPE_FLOW_ST_BLOCK 1024
+#define PPE_FLOW_SESS_WORDS 16u   /* u32 words of a session record (csrc/ppe_stream_session_dev.h has the layout) */
+#define PPE_STC_WORDS 64u         /* the counter block: struct tcpstream_track_stat's 58 fields, 6 spare words */
+/* the arguments of the one-launch flow kernel (its list pointers NULL in k and t: nothing is compacted before the
+ * sessions have spoken), then the lists, the session records of the table's current slot arrays, the counter block */
+struct ppe_flow_st_kargs {
+    struct ppe_kargs k;
+    struct ppe_flow_small_tail t;
+    uint32_t *fw_idx, *drop_idx, *tile_cnt;
+    uint8_t *part8;
+    uint32_t *sess;               /* nslots x PPE_FLOW_SESS_WORDS */
+    unsigned long long *stc;      /* PPE_STC_WORDS */
+};
+/* what the host passes beside the classify arguments and the tail */
+struct ppe_flow_st_args {
+    uint32_t *sess;
+    unsigned long long *stc;
+    uint32_t *tuple_scratch;      /* PPE_FLOW_ST_MAX x 4 words: the batch's tuples when the caller asks for none */
+};
+/* the pass behind a rehash: every live flow's record from the old slot arrays to the slot its key took in the new */
+struct ppe_flow_st_rehash_kargs {
+    const uint32_t *src_keys, *dst_keys;
+    const uint32_t *src_sess;
+    uint32_t *dst_sess;
+    uint32_t nslots, dst_gmask;
+};
+
 /* flow-hash steering across GPUs (ppe_steer_partition / ppe_gather_rows / ppe_scatter_rows) */
 #define PPE_STEER_MAX_WORLD 16
 struct ppe_steer_kargs {
@@ -516,6 +549,26 @@ uint32_t ppe_pick_flow_portscan(uint32_t n, int flow_attached, uint32_t able);
  * flow-attached and fps != PLAIN, with combine off or fps REFUSE) */
 enum { PPE_FPC_NONE = 0, PPE_FPC_KERNEL = 1, PPE_FPC_REFUSE = 2 };
 uint32_t ppe_pick_flow_combined(uint32_t fps, int atk_flow_attached, uint32_t combine_on);
+/* how a flow batch of n packets runs with respect to the TCP session machine: PPE_FST_PLAIN today's kernels (sessions
+ * not attached, or tracking off), PPE_FST_KERNEL the one-launch kernel with the session phase (1 <= n <=
+ * PPE_FLOW_ST_MAX), PPE_FST_REFUSE (PPE_ENOTSUP before anything is touched): a larger batch, a configuration other than
+ * {midstream 0, async_oneside 0, reasm 0}, or a port-scan table or monitors flow-attached as well */
+enum { PPE_FST_PLAIN = 0, PPE_FST_KERNEL = 1, PPE_FST_REFUSE = 2 };
+uint32_t ppe_pick_flow_stream(uint32_t n, int attached, uint32_t track, uint32_t midstream, uint32_t async_oneside,
+                              uint32_t reasm, int ps_flow_attached, int atk_flow_attached);
+/* the one-launch flow kernel with the session phase (csrc/ppe_kernels_flow_stream.hip): one workgroup of
+ * PPE_FLOW_ST_BLOCK threads, 1 <= a->batch[0].n <= PPE_FLOW_ST_MAX, a->batch[0].stride >= 144; a->flow.upd_wgs must be 0.
+ * Returns hipError_t */
+int ppe_launch_flow_stream(const struct ppe_kargs *a, const struct ppe_flow_small_tail *t,
+                           const struct ppe_flow_st_args *st, int mode, void *stream, void *ev_start, void *ev_stop);
+/* the session records' pass behind the flow rehash launch (same file).  Returns hipError_t */
+int ppe_launch_flow_stream_rehash(const struct ppe_flow_st_rehash_kargs *a, uint32_t grid, void *stream);
+/* The machine itself on the host, as the kernel compiles it (csrc/ppe_stream_session_dev.h, csrc/ppe_stream_session.cpp):
+ * one StreamTcpPacket step on a 16-word session record (the device layout).  pkt = {th_flags, seq, ack, window,
+ * payload_len, window-scale shift byte or 0xff without the option, toclient 0/1}; counters (64 words, may be NULL) get
+ * the fields counted.  Returns 0 or the reason.  No context, no device: the CPU tests hold it against the serial model
+ * (an internal helper like the planner's, not part of the public headers) */
+uint32_t ppe_stream_session_step(uint32_t record[16], const uint32_t pkt[7], uint64_t *counters);
 /* the monitors' set / tick / clear kernel (csrc/ppe_attack.hip), stream-ordered.  Returns hipError_t */
 int ppe_launch_attack_ctl(const struct ppe_atk_kargs *a, void *stream);
 /* one kernel of the port-scan pre-pass (csrc/ppe_portscan.hip), grid sized from the arguments.  Returns hipError_t */

@@ -2851,6 +2851,223 @@ __global__ __launch_bounds__(PPE_FLOW_PS_BLOCK) void ppe_flow_ps_kernel(ppe_flow
 }
 #endif
 
+#if defined(PPE_TU_FLOW_ST)
+#include "ppe_stream_session_dev.h"
+// One launch for a flow batch with the TCP session machine behind the table (csrc/ppe_kernels_flow_stream.hip; sessions
+// attached with ppe_flow_stream_attach, tracking on; 1 <= n <= PPE_FLOW_ST_MAX, ppe_pick_flow_stream):
+// FlowHandlePacket, then StreamTcp for every TCP packet that has a flow (flow.c:304-320), exactly as one core running
+// the batch in index order.  One workgroup of 1024 threads; thread p owns packet p from the session phase on.
+//   classify   classify_body<FLOW> with flow.upd_wgs = 0, as the one-launch kernel for small batches, writing the batch's
+//              tuples (the caller's array or the table's scratch) and no list: its list pointers are NULL;
+//   between    every wave drains its stores, the workgroup barrier, an agent-scope acquire-release fence in every wave;
+//   finalize   flow_finalize_wg<1024> with nwg = 1, its list pointers NULL: the flow decision per packet (found, creator,
+//              FLOW_NOMEM), FlowAdd / FlowUpdate, the verdict words and the 32 counters of the plain path.  The table is
+//              now exactly what the plain path leaves;
+//   between    drain, barrier, fence again: the verdicts, the tuples and the keys finalize made LIVE are read next;
+//   session    every TCP packet with a flow (ACL_FW with PPE_F_FLOW and PPE_F_TCP) finds its flow's slot (flow_find over
+//              the finished table) and puts slot << 32 | index and the values its step needs (th_flags, direction,
+//              window-scale shift, created-the-flow; seq; ack; window and payload length) into LDS; a bitonic sort of the
+//              keys over the batch's power of two groups the packets by slot in index order; the first packet of each
+//              group walks it: loads the slot's 64-B record, zeroes it at a PPE_F_NEWFLOW packet, steps
+//              ppe_stream_step packet by packet with the record in registers, leaves each reason in LDS, stores the
+//              record once.  The sort's stages and the walk (at most n steps: the loop runs over sorted positions below
+//              the sort length) are the only loops; no wait on another lane, no spin;
+//   finish     each thread completes its own packet: a reason turns ACL_FW into status 20-23 or
+//              PPE_ST_STREAM_TRACK_DROP with the reason in flag bits 10-15 and the action into DROP; every tile is
+//              compacted once, here; per stream drop OUT_FW gives one to OUT_DROP in this workgroup's counter slot (the
+//              plain phases counted the packet as forwarded: the adds are modulo 2^64 and ppe_counters_read sums the
+//              slots); the 58 stream counters go from LDS to the block by one atomic each.
+// Per word, what the later phases read and how:
+//   verdict[], tuple[]   classify's non-temporal and finalize's plain stores, drained; plain loads behind the fence;
+//   keys[]       finalize's LIVE stores, drained; flow_find's plain loads behind the fence; nothing stores keys after;
+//   hdr[]        read-only in the launch: plain byte loads;
+//   sess[]       a slot's record is loaded, stepped and stored by one thread, the slot's walker; written before this
+//                launch by an earlier launch on the stream, a rehash pass or a memset, all complete; vector loads and
+//                stores, nobody else reads it here;
+//   stc[], cslots[]   agent-scope atomic adds, read by nobody in the launch.
+constexpr uint32_t FST_NEW = 1u << 24;
+template <int MODE>
+__global__ __launch_bounds__(PPE_FLOW_ST_BLOCK) void ppe_flow_st_kernel(ppe_flow_st_kargs a) {
+    constexpr int BLOCK = PPE_FLOW_ST_BLOCK;
+    static_assert(sizeof(ppe_flow_st_kargs) <= 4096u, "HIP's limit for a kernel's explicit arguments");
+    static_assert(offsetof(ppe_flow_st_kargs, k) == 0u, "the classify arguments first, at ppe_kargs' own offsets");
+    static_assert(PPE_FLOW_ST_MAX <= (uint32_t)BLOCK, "one packet per thread");
+    static_assert(PPE_STC__COUNT <= PPE_STC_WORDS && PPE_STC_WORDS <= 64u, "the counter block");
+    classify_body<MODE, PF_HOIST, BLOCK, true>(a.k);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    {
+        // finalize's LDS: the first words of the key slots, as in ppe_flow_small_kernel
+        using L = Lds<BLOCK, true, 0u>;
+        static_assert(4u * (PPE_NBINS + 32u + BLOCK + (1u + 1u + 2u) + 4u) <= L::KEYB, "finalize's arrays fit the key slots");
+        uint32_t *bins = smem, *lcnt = bins + PPE_NBINS, *part = lcnt + 32u, *tail = part + BLOCK;
+        ppe_flow_kargs f = {};
+        f.f = a.k.flow;
+        f.len = a.t.len;
+        f.verdict = a.t.verdict;
+        f.hit = a.t.hit;
+        f.n = a.k.batch[0].n;
+        f.unsup_fw = a.k.unsup_fw;
+        f.now = a.k.now;
+        f.revoke = a.t.revoke;
+        f.fin_wgs = 1u;
+        f.cslots = a.k.cslots;
+        flow_finalize_wg<BLOCK, false>(f, 1u, bins, lcnt, part, tail[0], *(unsigned long long *)(tail + 2), tail + 4);
+    }
+    // ---- session ----
+    // LDS: what the classify phase had in front of the image, free behind the barrier
+    using LI = Lds<BLOCK, true, 4u * PPE_UPD_OWNERS * (1u + (PPE_UPD_LDS ? PPE_UPD_CAP : 0u))>;
+    static_assert(8u * BLOCK + 4u * (4u * BLOCK + PPE_STC_WORDS + 4u) <= LI::IMGB, "the session arrays fit in front of the image");
+    unsigned long long *keys = (unsigned long long *)smem;       // [BLOCK] slot << 32 | index, ~0 for the rest
+    uint32_t *pf = smem + 2u * BLOCK, *sq = pf + BLOCK, *ak = sq + BLOCK, *wp = ak + BLOCK;  // by packet index
+    uint32_t *sc = wp + BLOCK, *g = sc + PPE_STC_WORDS;          // the stream counters; g[0]: drops, g[1]: lost flows
+    const ppe_bdesc &B = a.k.batch[0];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // (the counters lie behind finalize's arrays, which its last loop may still be reading in another wave)
+    static_assert(PPE_NBINS + 32u + BLOCK + 8u <= 6u * BLOCK, "the counters lie behind finalize's arrays");
+    if (tid < PPE_STC_WORDS + 4u) sc[tid] = 0u;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");
+    const uint32_t n = B.n, ntiles = (n + 63u) >> 6, p = tid;
+    const bool valid = p < n;
+    uint32_t v = valid ? a.t.verdict[p] : 0u;
+    bool tracked = valid && (v & 0xffu) == PPE_ST_ACL_FW &&
+                   ((v >> 16) & (PPE_F_FLOW | PPE_F_TCP)) == (PPE_F_FLOW | PPE_F_TCP);
+    unsigned long long key = ~0ull;
+    if (tracked) {
+        const uint4 t = ((const uint4 *)B.tuple)[p];
+        uint32_t fsip = 0, fports = 0;
+        const int32_t s = flow_find(a.k.flow, flow_hashfn_l4(true, t.x, t.y, t.z & 0xffffu, t.z >> 16), t.x, t.y, t.z, 6u,
+                                    fsip, fports);
+        if (s >= 0) {
+            // the TCP header in the window: behind Ethernet, one VLAN tag if decoded, and the IPv4 header (stride >= 144
+            // holds every byte read here: at most 18 + 60 + 60)
+            const uint8_t *row = B.hdr + (size_t)p * B.stride;
+            const uint32_t l3 = 14u + (((t.w >> 8) & 1u) ? 4u : 0u);
+            const uint8_t *th = row + l3 + 4u * (row[l3] & 15u);
+            const uint32_t wso = PPE_TUPLE_WS(t.w);  // the option's offset from the TCP header, 0: none
+            const uint32_t ws = wso ? (uint32_t)th[wso + 2u] : (uint32_t)PPE_SS_NO_WS;
+            pf[p] = (uint32_t)th[13] | (((v >> 16) & PPE_F_TOCLIENT) ? 0x100u : 0u) | (ws << 16) |
+                    (((v >> 16) & PPE_F_NEWFLOW) ? FST_NEW : 0u);
+            sq[p] = ((uint32_t)th[4] << 24) | ((uint32_t)th[5] << 16) | ((uint32_t)th[6] << 8) | th[7];
+            ak[p] = ((uint32_t)th[8] << 24) | ((uint32_t)th[9] << 16) | ((uint32_t)th[10] << 8) | th[11];
+            wp[p] = ((uint32_t)th[14] << 8) | th[15] | ((t.w >> 16) << 16);
+            key = ((unsigned long long)(uint32_t)s << 32) | p;
+        } else {  // never: a packet with PPE_F_FLOW has a live flow when finalize is done
+            tracked = false;
+            g[1] = 1u;
+        }
+    }
+    keys[p] = key;
+    // bitonic sort of the keys over the batch's power of two (at least one wave)
+    uint32_t np2 = 64u;
+    while (np2 < n) np2 <<= 1;
+    for (uint32_t k = 2u; k <= np2; k <<= 1) {
+        for (uint32_t j = k >> 1; j > 0u; j >>= 1) {
+            __syncthreads();
+            const uint32_t q = tid ^ j;
+            if (tid < np2 && q > tid) {
+                const unsigned long long x = keys[tid], y = keys[q];
+                if ((x > y) == ((tid & k) == 0u)) {
+                    keys[tid] = y;
+                    keys[q] = x;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // the walk: the first packet of each slot's group
+    if (tid < np2) {
+        const unsigned long long k0 = keys[tid];
+        const uint32_t slot = (uint32_t)(k0 >> 32);
+        if (k0 != ~0ull && (tid == 0u || (uint32_t)(keys[tid - 1u] >> 32) != slot)) {
+            uint4 *rp = (uint4 *)(a.sess + (size_t)PPE_FLOW_SESS_WORDS * slot);
+            uint32_t w[PPE_FLOW_SESS_WORDS];
+            {
+                const uint4 r0 = rp[0], r1 = rp[1], r2 = rp[2], r3 = rp[3];
+                w[0] = r0.x, w[1] = r0.y, w[2] = r0.z, w[3] = r0.w, w[4] = r1.x, w[5] = r1.y, w[6] = r1.z, w[7] = r1.w;
+                w[8] = r2.x, w[9] = r2.y, w[10] = r2.z, w[11] = r2.w, w[12] = r3.x, w[13] = r3.y, w[14] = r3.z, w[15] = r3.w;
+            }
+            PpeSsn x;
+            ppe_ss_unpack(w, x);
+#pragma unroll 1
+            for (uint32_t j = tid; j < np2; ++j) {  // (at most n steps: the group ends where the slot changes)
+                const unsigned long long kj = keys[j];
+                if ((uint32_t)(kj >> 32) != slot || kj == ~0ull) break;
+                const uint32_t i = (uint32_t)kj & (BLOCK - 1u);
+                const uint32_t f = pf[i], wl = wp[i];
+                if (f & FST_NEW) x = PpeSsn{};  // FlowAdd gave the flow no session yet: the zero record
+                const PpeSsPkt pk = {f & 0xffu, sq[i], ak[i], wl & 0xffffu, wl >> 16, (f >> 16) & 0xffu, (f >> 8) & 1u};
+                sq[i] = ppe_stream_step(x, pk, [&](uint32_t c) { atomicAdd(&sc[c], 1u); });
+            }
+            ppe_ss_pack(x, w);
+            rp[0] = make_uint4(w[0], w[1], w[2], w[3]);
+            rp[1] = make_uint4(w[4], w[5], w[6], w[7]);
+            rp[2] = make_uint4(w[8], w[9], w[10], w[11]);
+            rp[3] = make_uint4(w[12], w[13], w[14], w[15]);
+        }
+    }
+    __syncthreads();
+    // ---- finish ----
+    const uint32_t reason = tracked ? sq[p] : 0u;
+    if (reason) {
+        const uint32_t st = reason <= PPE_STC_MIDSTREAM_DISABLE ? reason + 17u : (uint32_t)PPE_ST_STREAM_TRACK_DROP;
+        static_assert(PPE_STC_RST_BUT_NO_SESSION + 17u == PPE_ST_STREAM_RST_NO_SESSION &&
+                      PPE_STC_MIDSTREAM_DISABLE + 17u == PPE_ST_STREAM_MIDSTREAM_OFF, "StateNone's four reasons");
+        const uint32_t fl = (v >> 16) | (st == PPE_ST_STREAM_TRACK_DROP ? reason << PPE_F_STREAM_REASON_SHIFT : 0u);
+        v = st | ((uint32_t)PPE_ACT_DROP << 8) | (fl << 16);
+        a.t.verdict[p] = v;
+    }
+    if (wv < ntiles)  // (wave-uniform)
+        compact_tile(a.fw_idx, a.drop_idx, a.tile_cnt, n, 0u, wv, lane, valid, (v >> 8) & 0xffu, ~0u, a.part8);
+    const uint32_t nd = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(reason != 0u));
+    if (lane == 0 && nd) atomicAdd(&g[0], nd);
+    __syncthreads();
+    if (tid < PPE_STC__COUNT && sc[tid])
+        __hip_atomic_fetch_add(&a.stc[tid], (unsigned long long)sc[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tid == 64u && g[0]) {  // output_drop_proc instead of the forward the plain phases counted (flow.c:316-319)
+        __hip_atomic_fetch_add(&a.k.cslots[PPE_C_OUT_DROP], (unsigned long long)g[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add(&a.k.cslots[PPE_C_OUT_FW], 0ull - (unsigned long long)g[0], __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (tid == 128u && g[1])
+        __hip_atomic_fetch_add(&a.k.flow.ctl[PPE_FCTL_ERR], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Behind a flow rehash: every live TCP flow's session record to the slot its key took in the new slot arrays.  One
+// thread per old slot; the probe is bounded by the new table's groups (the key is there: the rehash launch ahead of this
+// one on the stream inserted every live flow).
+__global__ __launch_bounds__(256) void ppe_flow_st_rehash_kernel(ppe_flow_st_rehash_kargs a) {
+    for (uint32_t s = blockIdx.x * 256u + threadIdx.x; s < a.nslots; s += gridDim.x * 256u) {
+        const uint4 k = ((const uint4 *)a.src_keys)[(size_t)(PPE_FLOW_SLOT_WORDS / 4u) * s];
+        if (k.w != PPE_FS_LIVE(6u)) continue;
+        uint32_t gq = key_hash(k.x, k.y, k.z, 6u) & a.dst_gmask;
+        bool done = false;
+#pragma unroll 1
+        for (uint32_t it = 0; it <= a.dst_gmask && !done; ++it) {
+#pragma unroll 1
+            for (uint32_t j = 0; j < PPE_FLOW_GROUP && !done; ++j) {
+                const uint32_t d = PPE_FLOW_GROUP * gq + j;
+                const uint4 e = ((const uint4 *)a.dst_keys)[(size_t)(PPE_FLOW_SLOT_WORDS / 4u) * d];
+                if (e.w == k.w && e.x == k.x && e.y == k.y && e.z == k.z) {
+                    const uint4 *sp = (const uint4 *)(a.src_sess + (size_t)PPE_FLOW_SESS_WORDS * s);
+                    uint4 *dp = (uint4 *)(a.dst_sess + (size_t)PPE_FLOW_SESS_WORDS * d);
+                    dp[0] = sp[0];
+                    dp[1] = sp[1];
+                    dp[2] = sp[2];
+                    dp[3] = sp[3];
+                    done = true;
+                }
+            }
+            gq = (gq + 1u) & a.dst_gmask;
+        }
+    }
+}
+#endif
+
 // FlowTimeOut + FlowAgeTimeoutCB (flow.c:391-467): live flows idle for more than `timeout` become tombstones.
 template <int BLOCK>
 __global__ __launch_bounds__(BLOCK) void ppe_flow_age_kernel(ppe_flow_kargs a) {
@@ -3151,6 +3368,46 @@ extern "C" int ppe_launch_classify_attack_flow(const ppe_kargs *a, uint32_t grid
 extern "C" int ppe_launch_flow_post_attack(const ppe_flow_kargs *a, uint32_t grid, size_t shmem, void *stream) {
     hipLaunchKernelGGL(ppe_flow_post_attack_kernel<PPE_FLOW_POST_BLOCK>, dim3(grid), dim3(PPE_FLOW_POST_BLOCK), shmem,
                        (hipStream_t)stream, *a);
+    return (int)hipGetLastError();
+}
+#elif defined(PPE_TU_FLOW_ST)
+// csrc/ppe_kernels_flow_stream.hip: this file again (as csrc/ppe_kernels_flow_small.hip builds it: classify_body as a
+// function, finalize over LDS its kernel provides), exporting only the one-launch flow kernel with the TCP session
+// machine behind it over the three image placements of the flow-table plan, at 1024 threads, and the session records'
+// pass behind a rehash
+extern "C" int ppe_launch_flow_stream(const ppe_kargs *a, const ppe_flow_small_tail *t, const ppe_flow_st_args *st,
+                                      int mode, void *stream, void *ev_start, void *ev_stop) {
+    const hipStream_t s = (hipStream_t)stream;
+    const hipEvent_t e0 = (hipEvent_t)ev_start, e1 = (hipEvent_t)ev_stop;
+    if (a->flow.upd_wgs != 0u || a->nbatch != 1u || a->ring || a->batch[0].n == 0u || a->batch[0].n > PPE_FLOW_ST_MAX ||
+        a->batch[0].stride < PPE_FLOW_STREAM_MIN_STRIDE || !st || !st->sess || !st->stc || !t->verdict)
+        return (int)hipErrorInvalidValue;
+    if (!a->batch[0].tuple && !st->tuple_scratch) return (int)hipErrorInvalidValue;
+    ppe_flow_st_kargs k;
+    k.k = *a;
+    k.t = *t;
+    // the lists are compacted once, by the kernel's last phase: the classify and finalize phases get none
+    k.fw_idx = t->fw_idx;
+    k.drop_idx = t->drop_idx;
+    k.tile_cnt = t->tile_cnt;
+    k.part8 = t->part8;
+    k.t.fw_idx = k.t.drop_idx = k.t.tile_cnt = nullptr;
+    k.t.part8 = nullptr;
+    k.k.batch[0].fw_idx = k.k.batch[0].drop_idx = k.k.batch[0].tile_cnt = nullptr;
+    k.k.batch[0].flags &= ~(uint32_t)PPE_BD_PART8;
+    if (!k.k.batch[0].tuple) k.k.batch[0].tuple = st->tuple_scratch;  // the session phase reads the batch's tuples
+    k.sess = st->sess;
+    k.stc = st->stc;
+    const size_t base = ppe_classify_fixed_lds(PPE_FLOW_ST_BLOCK, PF_HOIST, mode) + ppe_flow_lds_extra();
+    const size_t shmem = mode == IMG_GLOBAL ? base : base + (((size_t)a->stage_words * 4u + 1023u) & ~(size_t)1023u);
+    const dim3 g(1), b(PPE_FLOW_ST_BLOCK);
+    if (mode == IMG_LDS) hipExtLaunchKernelGGL((ppe_flow_st_kernel<IMG_LDS>), g, b, shmem, s, e0, e1, 0, k);
+    else if (mode == IMG_SPLIT) hipExtLaunchKernelGGL((ppe_flow_st_kernel<IMG_SPLIT>), g, b, shmem, s, e0, e1, 0, k);
+    else hipExtLaunchKernelGGL((ppe_flow_st_kernel<IMG_GLOBAL>), g, b, shmem, s, e0, e1, 0, k);
+    return (int)hipGetLastError();
+}
+extern "C" int ppe_launch_flow_stream_rehash(const ppe_flow_st_rehash_kargs *a, uint32_t grid, void *stream) {
+    hipLaunchKernelGGL(ppe_flow_st_rehash_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, *a);
     return (int)hipGetLastError();
 }
 #elif defined(PPE_TU_FLOW_SMALL)

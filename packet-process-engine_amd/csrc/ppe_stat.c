@@ -254,6 +254,44 @@ int ppe_format_tcpstream_stat(const ppe_stream_counters_t *c, const ppe_stream_t
     return (int)o.len;
 }
 
+/* the same text from the session path's block (ppe_stream_track_counters_t: all 58 fields of tcpstream_track_stat in
+ * the struct's order): every track line from the field of its own name, the reassembly lines 0 */
+static const char *const k_stc_names[PPE_STC__COUNT] = {
+    "SYN_ACK_COUNT", "SYN_COUNT", "RST_COUNT", "RST_BUT_NO_SESSION", "FIN_BUT_NO_SESSION",
+    "MIDSTREAM_OR_ONESIDE_DISABLE", "MIDSTREAM_DISABLE", "ONESIDE_DISABLE", "SESSION_NO_MEM", "FIN_INVALID_ACK",
+    "FIN_OUT_OF_WINDOW", "SESSION_PARAM_ERR", "WHS3_SYNACK_TOSERVER_SYN_RECV", "WHS3_SYNACK_SEQ_MISMATCH",
+    "WHS3_SYNACK_RESEND_WITH_DIFFERENT_ACK", "WHS3_SYN_TOCLIENT_ON_SYN_RECV", "WHS3_SYN_RESEND_DIFF_SEQ_ON_SYN_RECV",
+    "WHS3_SYNACK_IN_WRONG_DIRECTION", "WHS3_ACK_IN_WRONG_DIR", "WHS3_RIGHT_SEQ_WRONG_ACK_EVASION",
+    "WHS3_WRONG_SEQ_WRONG_ACK", "WHS3_ASYNC_WRONG_SEQ", "WHS3_SYNACK_WITH_WRONG_ACK", "WHS4_WRONG_SEQ",
+    "WHS4_INVALID_ACK", "WHS4_SYNACK_WITH_WRONG_ACK", "WHS4_SYNACK_WITH_WRONG_SYN", "EST_INVALID_ACK",
+    "EST_PKT_BEFORE_LAST_ACK", "EST_PACKET_OUT_OF_WINDOW", "EST_SYNACK_RESEND", "EST_SYNACK_TOSERVER",
+    "EST_SYNACK_RESEND_WITH_DIFFERENT_ACK", "EST_SYNACK_RESEND_WITH_DIFF_SEQ", "EST_SYN_TOCLIENT",
+    "EST_SYN_RESEND_DIFF_SEQ", "EST_SYN_RESEND", "PKT_RETRANSMISSION", "FIN2_FIN_WRONG_SEQ", "FIN2_INVALID_ACK",
+    "FIN2_ACK_WRONG_SEQ", "FIN1_FIN_WRONG_SEQ", "FIN1_INVALID_ACK", "FIN1_ACK_WRONG_SEQ", "SHUTDOWN_SYN_RESEND",
+    "CLOSEWAIT_FIN_OUT_OF_WINDOW", "CLOSING_ACK_WRONG_SEQ", "CLOSEWAIT_INVALID_ACK", "CLOSING_INVALID_ACK",
+    "CLOSEWAIT_PKT_BEFORE_LAST_ACK", "CLOSEWAIT_ACK_OUT_OF_WINDOW", "LASTACK_ACK_WRONG_SEQ", "LASTACK_INVALID_ACK",
+    "TIMEWAIT_ACK_WRONG_SEQ", "TIMEWAIT_INVALID_ACK", "PKT_INVALID_ACK", "PKT_BAD_WINDOW_UPDATE", "PKT_BROKEN_ACK"};
+
+int ppe_format_tcpstream_stat_ex(const ppe_stream_track_counters_t *c, const ppe_stream_tcp_cfg_t *cfg, char *buf,
+                                 size_t cap) {
+    if (!c) return PPE_EINVAL;
+    out_t o = {buf, buf ? cap : 0, 0};
+    if (buf && cap) buf[0] = 0;
+    put(&o, "tcpstream statistic:\n");
+    put(&o, "tcpstream track: %s\n", cfg && cfg->track ? "enable" : "disable");
+    put(&o, "tcpstream reasm: %s\n", cfg && cfg->reasm ? "enable" : "disable");
+    put(&o, "----------------------------------\n");
+    for (size_t i = 0; i < sizeof k_tcpstream / sizeof k_tcpstream[0]; i++) {
+        long v = 0;
+        for (int k = 0; k < PPE_STC__COUNT; k++)
+            if (strcmp(k_tcpstream[i].name, k_stc_names[k]) == 0) v = (long)c->c[k];
+        put(&o, "%s: %ld\n", k_tcpstream[i].name, v);
+    }
+    put(&o, "----------------\n");
+    put(&o, "\n");
+    return (int)o.len;
+}
+
 int ppe_format_flow_stat(const ppe_flow_info_t *f, char *buf, size_t cap) {
     return ppe_format_flow_stat_ex(f, NULL, buf, cap);
 }

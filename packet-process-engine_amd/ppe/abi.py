@@ -27,10 +27,30 @@ ST = dict(ACL_FW=0, ACL_DROP=1, L2_HEADER_ERR=2, L2_UNSUPPORT=3, VLAN_HEADER_ERR
           # PortScan_Detect's drop (a table attached with ppe_portscan_attach)
           PORTSCAN_DROP=24,
           # the attack monitors' drops (an object attached with ppe_attack_attach)
-          ATTACK_LAND=25, ATTACK_SYNFLOOD=26, ATTACK_SYNCOUNT=27, ATTACK_UDPFLOOD=28)
+          ATTACK_LAND=25, ATTACK_SYNFLOOD=26, ATTACK_SYNCOUNT=27, ATTACK_UDPFLOOD=28,
+          # the TCP session machine's drop on the flow path (ppe_flow_stream_attach); the reason in flag bits 10-15
+          STREAM_TRACK_DROP=29)
 ST_COUNT, ST_END = 24, 25  # PPE_ST__COUNT (statuses without a port-scan table), PPE_ST__END (with one)
 ST_ALL = 29                # PPE_ST__ALL (every status, the attack monitors' included)
+ST_ALL2 = 30               # PPE_ST__ALL2 (every status, PPE_ST_STREAM_TRACK_DROP included)
 ST_NAME = {v: k for k, v in ST.items()}
+F_STREAM_REASON_SHIFT = 10  # PPE_F_STREAM_REASON_SHIFT
+# enum ppe_stream_track_counter (ppe_stream_track_counters_t.c[]): struct tcpstream_track_stat's fields, in order
+STREAM_TRACK_COUNTERS = [
+    "SYN_ACK_COUNT", "SYN_COUNT", "RST_COUNT", "RST_BUT_NO_SESSION", "FIN_BUT_NO_SESSION",
+    "MIDSTREAM_OR_ONESIDE_DISABLE", "MIDSTREAM_DISABLE", "ONESIDE_DISABLE", "SESSION_NO_MEM", "FIN_INVALID_ACK",
+    "FIN_OUT_OF_WINDOW", "SESSION_PARAM_ERR", "WHS3_SYNACK_TOSERVER_SYN_RECV", "WHS3_SYNACK_SEQ_MISMATCH",
+    "WHS3_SYNACK_RESEND_WITH_DIFFERENT_ACK", "WHS3_SYN_TOCLIENT_ON_SYN_RECV", "WHS3_SYN_RESEND_DIFF_SEQ_ON_SYN_RECV",
+    "WHS3_SYNACK_IN_WRONG_DIRECTION", "WHS3_ACK_IN_WRONG_DIR", "WHS3_RIGHT_SEQ_WRONG_ACK_EVASION",
+    "WHS3_WRONG_SEQ_WRONG_ACK", "WHS3_ASYNC_WRONG_SEQ", "WHS3_SYNACK_WITH_WRONG_ACK", "WHS4_WRONG_SEQ",
+    "WHS4_INVALID_ACK", "WHS4_SYNACK_WITH_WRONG_ACK", "WHS4_SYNACK_WITH_WRONG_SYN", "EST_INVALID_ACK",
+    "EST_PKT_BEFORE_LAST_ACK", "EST_PACKET_OUT_OF_WINDOW", "EST_SYNACK_RESEND", "EST_SYNACK_TOSERVER",
+    "EST_SYNACK_RESEND_WITH_DIFFERENT_ACK", "EST_SYNACK_RESEND_WITH_DIFF_SEQ", "EST_SYN_TOCLIENT",
+    "EST_SYN_RESEND_DIFF_SEQ", "EST_SYN_RESEND", "PKT_RETRANSMISSION", "FIN2_FIN_WRONG_SEQ", "FIN2_INVALID_ACK",
+    "FIN2_ACK_WRONG_SEQ", "FIN1_FIN_WRONG_SEQ", "FIN1_INVALID_ACK", "FIN1_ACK_WRONG_SEQ", "SHUTDOWN_SYN_RESEND",
+    "CLOSEWAIT_FIN_OUT_OF_WINDOW", "CLOSING_ACK_WRONG_SEQ", "CLOSEWAIT_INVALID_ACK", "CLOSING_INVALID_ACK",
+    "CLOSEWAIT_PKT_BEFORE_LAST_ACK", "CLOSEWAIT_ACK_OUT_OF_WINDOW", "LASTACK_ACK_WRONG_SEQ", "LASTACK_INVALID_ACK",
+    "TIMEWAIT_ACK_WRONG_SEQ", "TIMEWAIT_INVALID_ACK", "PKT_INVALID_ACK", "PKT_BAD_WINDOW_UPDATE", "PKT_BROKEN_ACK"]
 # enum ppe_stream_counter (ppe_stream_counters_t.c[])
 STREAM_COUNTERS = ["syn_ack_count", "syn_count", "rst_count", "rst_but_no_session", "fin_but_no_session",
                    "midstream_or_oneside_disable", "midstream_disable", "pkt_broken_ack"]
@@ -119,6 +139,30 @@ class StreamCounters(C.Structure):  # ppe_stream_counters_t
 
     def as_dict(self):
         return {name: int(self.c[i]) for i, name in enumerate(STREAM_COUNTERS)}
+
+
+class StreamTrackCounters(C.Structure):  # ppe_stream_track_counters_t
+    _fields_ = [("c", C.c_uint64 * 64)]
+
+    def as_list(self):
+        return [int(self.c[i]) for i in range(len(STREAM_TRACK_COUNTERS))]
+
+    def as_dict(self):
+        return dict(zip(STREAM_TRACK_COUNTERS, self.as_list()))
+
+
+class StreamSide(C.Structure):  # ppe_stream_side_t
+    _fields_ = [("isn", C.c_uint32), ("next_seq", C.c_uint32), ("last_ack", C.c_uint32), ("next_win", C.c_uint32),
+                ("window", C.c_uint32), ("flags", C.c_uint16), ("wscale", C.c_uint8), ("pad", C.c_uint8)]
+
+    def astuple(self):  # in the order of tests/stream_session_model.py's Stream
+        return (self.flags, self.wscale, self.isn, self.next_seq, self.last_ack, self.next_win, self.window)
+
+
+class FlowStreamEntry(C.Structure):  # ppe_flow_stream_entry_t
+    _fields_ = [("sip", C.c_uint32), ("dip", C.c_uint32), ("sport", C.c_uint16), ("dport", C.c_uint16),
+                ("slot", C.c_uint32), ("flags", C.c_uint16), ("state", C.c_uint8), ("pad", C.c_uint8),
+                ("client", StreamSide), ("server", StreamSide)]
 
 
 class PortScanCfg(C.Structure):  # ppe_portscan_cfg_t
@@ -339,6 +383,8 @@ EXPORTS = [
     "ppe_pick_defrag_small_upto", "ppe_defrag_small_upto_from_env",
     "ppe_stream_tcp_set", "ppe_stream_tcp_get", "ppe_stream_counters_read", "ppe_stream_counters_clear",
     "ppe_format_tcpstream_stat",
+    "ppe_flow_stream_attach", "ppe_flow_stream_max", "ppe_flow_stream_dump", "ppe_stream_track_counters_read",
+    "ppe_stream_track_counters_clear", "ppe_format_tcpstream_stat_ex",
     "ppe_portscan_create", "ppe_portscan_destroy", "ppe_portscan_attach", "ppe_portscan_clock", "ppe_portscan_set",
     "ppe_portscan_age", "ppe_portscan_info", "ppe_portscan_dump", "ppe_portscan_last_error", "ppe_portscan_prepass_info",
     "ppe_flow_portscan_attach", "ppe_flow_portscan_max", "ppe_flow_portscan_rounds", "ppe_flow_combine",
@@ -348,7 +394,8 @@ EXPORTS = [
     "ppe_format_attack_stat", "ppe_format_pkt_stat_atk",
     # csrc/ppe_internal.h: the host-only launch planner (internal helpers, not part of the public headers)
     "ppe_plan_image", "ppe_pick_groups", "ppe_pick_portscan", "ppe_pick_portscan_prepass", "ppe_pick_attack", "ppe_pick_attack_flow", "ppe_pick_flow_small",
-    "ppe_pick_flow_portscan", "ppe_pick_flow_combined", "ppe_pick_flow_small_attack",
+    "ppe_pick_flow_portscan", "ppe_pick_flow_combined", "ppe_pick_flow_small_attack", "ppe_pick_flow_stream",
+    "ppe_stream_session_step",
     # ppe_acl.h
     "ppe_rule_list_init", "ppe_rule_list_free", "Rule_add", "Rule_del_by_id", "Rule_del_all",
     "Rule_duplicate_check", "Rule_Load_Line", "ppe_rule_load_file", "DP_Acl_Rule_Init", "DP_Acl_Load_Rule",
@@ -439,6 +486,15 @@ def _open(p: Path, mode, strict: bool = True) -> C.CDLL:
         "ppe_pick_flow_portscan": ([u32, C.c_int, u32], u32),
         "ppe_flow_portscan_attach": ([vp, vp], C.c_int),
         "ppe_flow_portscan_max": ([], u32),
+        "ppe_flow_stream_attach": ([vp, u32], C.c_int),
+        "ppe_flow_stream_max": ([], u32),
+        "ppe_flow_stream_dump": ([vp, C.POINTER(FlowStreamEntry), u32, C.POINTER(u32)], C.c_int),
+        "ppe_stream_track_counters_read": ([vp, C.POINTER(StreamTrackCounters)], C.c_int),
+        "ppe_stream_track_counters_clear": ([vp], C.c_int),
+        "ppe_format_tcpstream_stat_ex": ([C.POINTER(StreamTrackCounters), C.POINTER(StreamTcpCfg), C.c_char_p,
+                                          C.c_size_t], C.c_int),
+        "ppe_stream_session_step": ([C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_uint64)], u32),
+        "ppe_pick_flow_stream": ([u32, C.c_int, u32, u32, u32, u32, C.c_int, C.c_int], u32),
         "ppe_flow_portscan_rounds": ([vp, C.POINTER(u32)], C.c_int),
         "ppe_flow_combine": ([vp, u32], C.c_int),
         "ppe_pick_flow_combined": ([u32, C.c_int, u32], u32),

@@ -315,6 +315,35 @@ class Engine:
     def clear_stream_counters(self):
         self._check(self.lib.ppe_stream_counters_clear(self.ctx), "ppe_stream_counters_clear")
 
+    # ---- StreamTcp's session state machine behind the flow table (ppe_flow_stream_*, stream-tcp.c StreamTcpPacket) ----
+    def flow_stream(self, on: int = 1) -> None:
+        """ppe_flow_stream_attach: 1, later flow batches run every TCP packet that has a flow through its flow's session
+        (with stream_tcp(track=1, reasm=0); flow_launch_info (5, 1)); every session record is zeroed.  0: the plain
+        kernels again.  Needs a flow table."""
+        self._check(self.lib.ppe_flow_stream_attach(self.ctx, int(on)), "ppe_flow_stream_attach")
+
+    def flow_stream_max(self) -> int:
+        """ppe_flow_stream_max: the packets one device flow batch takes with sessions attached."""
+        return int(self.lib.ppe_flow_stream_max())
+
+    def flow_stream_dump(self) -> list:
+        """ppe_flow_stream_dump: every live TCP flow's key and session record (abi.FlowStreamEntry), in table order."""
+        n = C.c_uint32(0)
+        self._check(self.lib.ppe_flow_stream_dump(self.ctx, None, 0, C.byref(n)), "ppe_flow_stream_dump")
+        out = (abi.FlowStreamEntry * max(1, n.value))()
+        if n.value:
+            self._check(self.lib.ppe_flow_stream_dump(self.ctx, out, n.value, C.byref(n)), "ppe_flow_stream_dump")
+        return list(out[:n.value])
+
+    def stream_track_counters(self) -> dict:
+        """ppe_stream_track_counters_read: the 58 fields of tcpstream_track_stat the session path counts, by name."""
+        c = abi.StreamTrackCounters()
+        self._check(self.lib.ppe_stream_track_counters_read(self.ctx, C.byref(c)), "ppe_stream_track_counters_read")
+        return c.as_dict()
+
+    def clear_stream_track_counters(self):
+        self._check(self.lib.ppe_stream_track_counters_clear(self.ctx), "ppe_stream_track_counters_clear")
+
     # ---- port-scan detector (ppe_portscan_*, dataplane/src/attack/dp_portscan.c) ----
     def portscan(self, attach: bool = True, **cfg) -> "PortScan":
         """ppe_portscan_create (cfg: the words of ppe_portscan_cfg_t; none given = the reference's defaults) and, unless
