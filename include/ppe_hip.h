@@ -482,8 +482,8 @@ int ppe_classify_flow_host_ports(ppe_ctx_t *ctx, const ppe_batch_t *in, const pp
  * one-launch kernel with the port-scan detector inside, ppe_flow_portscan_attach), 3 and 1 (that kernel with the
  * flow-attached attack monitors in it as well, ppe_flow_combine), 4 and 1 (the one-launch kernel with the
  * flow-attached monitors in it: chunks of ppe_classify_flow_host_ports only), or 0 and 2; 0 and 0 before the first
- * batch; 5 and 1: the one-launch kernel with the TCP session machine behind it (ppe_flow_stream_attach).  NULL
- * arguments: PPE_EINVAL. */
+ * batch; 5 and 1: the one-launch kernel with the TCP session machine behind it (ppe_flow_stream_attach); 6 and 1:
+ * that kernel with the flow-attached monitors in it as well (ppe_flow_stream_monitors).  NULL arguments: PPE_EINVAL. */
 int  ppe_flow_launch_info(ppe_ctx_t *ctx, uint32_t *kind, uint32_t *launches);
 /* FlowAgeTimeoutCB: delete flows with now > last_seen && now - last_seen > timeout_seconds; *deleted = count
  * (may be NULL).  Synchronises. */
@@ -518,7 +518,8 @@ int  ppe_flow_dump(ppe_ctx_t *ctx, ppe_flow_entry_t *entries, uint32_t max, uint
  *   rehash moves the records with their flows.  Not kept: ra_app_base_seq, ra_raw_base_seq, last_ts, last_pkt_ts,
  *   os_policy, the segment lists.
  * Refused before anything is touched: attached with track 1 and any of reasm, midstream, async_oneside 1
- * (PPE_ENOTSUP); a port-scan table or monitors flow-attached at the same time (PPE_ENOTSUP); a device batch of more
+ * (PPE_ENOTSUP); a port-scan table flow-attached at the same time, or monitors flow-attached unless
+ * ppe_flow_stream_monitors is on (PPE_ENOTSUP); a device batch of more
  * than ppe_flow_stream_max() packets (PPE_ENOTSUP; ppe_classify_flow_host takes host batches of any size in chunks
  * of at most that); a header stride under 144 B (PPE_EINVAL: neither PPE_ST_WINDOW_PUNT nor PPE_TUPLE_OPT_PAST may
  * stand between a SYN and its window scale); attach without a flow table (PPE_EINVAL).  Attached with track 0 the
@@ -534,11 +535,38 @@ typedef struct {
     uint16_t sport, dport;
     uint32_t slot;                /* device table slot (diagnostic) */
     uint16_t flags;               /* STREAMTCP_FLAG_* */
-    uint8_t  state, pad;
+    uint8_t  state, pad;          /* pad: the flow's input port, flow_item_t.input_port (ppe_flow_stream_monitors; else 0) */
     ppe_stream_side_t client, server;
 } ppe_flow_stream_entry_t;
 /* Copy up to `max` live TCP flows with their sessions to host (table order); *n = live TCP flows.  Synchronises. */
 int  ppe_flow_stream_dump(ppe_ctx_t *ctx, ppe_flow_stream_entry_t *entries, uint32_t max, uint32_t *n);
+/* ---- Monitors flow-attached and sessions attached on one batch: syncount_accum as the gauge of half-open connections ----
+ * 0 (a new context): as before, the two together are refused.  1: with sessions attached, ppe_stream_tcp_set holding
+ * {1,0,0,0}, an object attached with ppe_flow_attack_attach and no port-scan table flow-attached, ppe_classify_flow takes
+ * a batch of 1 <= n <= ppe_flow_stream_max() packets (stride >= PPE_FLOW_STREAM_MIN_STRIDE) in one launch
+ * (ppe_flow_launch_info kind 6), exactly one core running the batch in index order: the monitors first, for every packet,
+ * as under ppe_flow_attack_attach alone (a packet they drop reaches neither the table nor its session: a SYN|ACK the
+ * SYN-flood monitor drops leaves its session in SYN_SENT); the survivors take ppe_flow_stream_attach's path unchanged.
+ * on > 1: PPE_EINVAL.  The context's, like ppe_flow_combine: ppe_flow_destroy leaves it; no synchronisation.
+ *   syncount_accum: +1 on the packet's port for a TCP SYN that ends with PPE_F_NEWFLOW, as under ppe_flow_attack_attach
+ *   (FlowAdd runs before StreamTcp: whatever the session's verdict); -1 on the port of the packet whose step takes its
+ *   session from SYN_RECV to ESTABLISHED (DP_Attack_SynCountFins, stream-tcp.c:608 and :660, on m->input_port: that
+ *   packet's port, not the flow's); -1 on the flow's port for every TCP flow ppe_flow_age deletes while its session is
+ *   in the handshake (StreamTcp_Flow_ResRelease, stream-tcp-session.c:61-77: state not NONE and at most SYN_RECV), once
+ *   per deleted flow, visible to the next ppe_attack_info and folded by the next ppe_attack_tick, whatever track is.
+ *   The flow's port is its creating packet's (flow_item_t.input_port, flow.c:139; a flow created while no monitors were
+ *   flow-attached, or by the kernel without them: port 0); ppe_flow_stream_dump reports it in `pad`.
+ *   The arithmetic is the reference's cvmx_atomic_add64 on a uint64_t, modulo 2^64, and so is this: a port that
+ *   establishes more than it created in an interval (a handshake that completes on another port than its SYN's, or a
+ *   session reused from CLOSED, which takes a second -1 with no +1) shows syncount_accum: -1 in ppe_format_attack_stat,
+ *   its syncount is 2^64 - 1 after the tick, and with td.drop_pack 1 every SYN on it is then PPE_ST_ATTACK_SYNCOUNT
+ *   until the next tick.  That is the reference's behaviour, reproduced.
+ * ppe_classify_flow_host_ports runs host batches of any size under the same conditions (chunks of at most
+ * ppe_flow_stream_max(), each one launch with its slice of `ports`); ppe_classify_flow_host keeps refusing monitors
+ * flow-attached.  Still refused before anything is touched: the switch off, a port-scan table flow-attached as well
+ * (whatever its able), a larger device batch, reasm / midstream / async_oneside 1 (PPE_ENOTSUP); a stride under 144 B
+ * (PPE_EINVAL).  With the switch on but only one of the two attached, or track 0, nothing changes. */
+int  ppe_flow_stream_monitors(ppe_ctx_t *ctx, uint32_t on);
 /* struct tcpstream_track_stat (decode-statistic.h:118-179), every field in the reference's order; the session path
  * counts here (the stateless path keeps feeding ppe_stream_counters_t) */
 enum ppe_stream_track_counter {
@@ -849,7 +877,8 @@ int  ppe_flow_combine(ppe_ctx_t *ctx, uint32_t on);
  *     flood_syn).
  *   syncount_accum++ (FlowAdd, flow.c:151-154) for every TCP SYN packet whose status is PPE_ST_ACL_FW after the
  *   port-scan mask and before StreamTcp's verdict: on this path every packet that reaches FlowAdd is the first of its
- *   flow.  The decrements (stream-tcp.c:608,660, stream-tcp-session.c:70) belong to the session machine: not built.
+ *   flow.  The decrements (stream-tcp.c:608,660, stream-tcp-session.c:70) belong to the session machine: on the
+ *   flow-table path with ppe_flow_stream_monitors, not on this one.
  * Not judged and not counted: fragments, PPE_ST_WINDOW_PUNT, anything that fails before the IPv4 protocol dispatch,
  * a TCP packet that fails a length check or has no SYN.  A reassembled datagram classified afterwards counts once (the
  * reference adds one per fragment, dp_attack.c:586-601: a known difference).  ICMP never reaches its monitors in the
@@ -911,8 +940,8 @@ int  ppe_attack_attach(ppe_ctx_t *ctx, ppe_attack_t *atk);        /* NULL detach
  *     later SYN of the same 5-tuple in the batch, not a SYN of a live flow, not a creator refused with
  *     PPE_ST_FLOW_NOMEM, not an ACL drop or FLOW_TCP_NO_SYN_FIRST, not a UDP or non-SYN TCP packet that creates a flow.
  *     (The stateless path counts every forwarded SYN: there every packet is a flow miss.)
- * Everything else is as above: the tick, set, clock, info, clear_stat, the show texts, the hold arming.  Still not
- * built: syncount_accum's decrements (the session machine), per-fragment counting, ICMP.
+ * Everything else is as above: the tick, set, clock, info, clear_stat, the show texts, the hold arming.  syncount_accum's
+ * decrements take the sessions as well (ppe_flow_stream_monitors).  Still not built: per-fragment counting, ICMP.
  * ppe_classify_flow is one batch per call: it reads entry 0 of ppe_attack_ports' table (NULL or none: port 0), at the
  * call, by value.  Calls go through one stream or are ordered by the caller; ppe_attack_set / _tick apply to the
  * launches enqueued after them, without a synchronise.

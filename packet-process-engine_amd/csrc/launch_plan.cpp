@@ -396,4 +396,17 @@ uint32_t ppe_pick_flow_stream(uint32_t n, int attached, uint32_t track, uint32_t
     return n <= PPE_FLOW_ST_MAX ? PPE_FST_KERNEL : PPE_FST_REFUSE;
 }
 
+// the same with the context's switch for monitors and sessions on one batch (ppe_flow_stream_monitors;
+// csrc/ppe_kernels_flow_stream_attack.hip): off, ppe_pick_flow_stream's answer; on, monitors flow-attached beside the
+// sessions take the kernel with both inside, and everything else is as without the switch (a port-scan table
+// flow-attached as well, whatever its `able`, is still refused)
+uint32_t ppe_pick_flow_stream_monitors(uint32_t n, int attached, uint32_t track, uint32_t midstream,
+                                       uint32_t async_oneside, uint32_t reasm, int ps_flow_attached,
+                                       int atk_flow_attached, uint32_t monitors_on) {
+    if (monitors_on != 1u || !atk_flow_attached)
+        return ppe_pick_flow_stream(n, attached, track, midstream, async_oneside, reasm, ps_flow_attached, atk_flow_attached);
+    const uint32_t r = ppe_pick_flow_stream(n, attached, track, midstream, async_oneside, reasm, ps_flow_attached, 0);
+    return r == PPE_FST_KERNEL ? PPE_FST_KERNEL_ATK : r;
+}
+
 }  // extern "C"

@@ -223,6 +223,7 @@ struct ppe_ctx {
     ppe_attack *atk = nullptr;         // ppe_attack_attach
     ppe_attack *atk_flow = nullptr;    // ppe_flow_attack_attach: ppe_classify_flow's monitors (never the same object as atk)
     uint32_t flow_combine = 0;         // ppe_flow_combine: ps_flow (able 1) and atk_flow on one batch, in one launch
+    uint32_t flow_st_monitors = 0;     // ppe_flow_stream_monitors: atk_flow and the sessions on one batch, in one launch
     unsigned long long *d_stc = nullptr;  // the session path's counter block (PPE_STC_WORDS), from the first attach on
     FlowTable *flow = nullptr;  // ppe_flow_create
     LookupStage lk;             // ppe_acl_lookup_host
@@ -679,12 +680,13 @@ int ps_prepass(ppe_ctx *c, const ppe_batch_t *in, uint32_t nb, const ppe_cfg_t *
 // (fps_atk: the one with the flow-attached monitors in it as well); small_atk: the one-launch kernel of small with
 // the flow-attached monitors in it; fatk_pb_set: the flow-attached monitors read the port bytes fatk_pb (device
 // pointer or NULL) instead of the sticky table's entry 0; fst (with small): the one-launch kernel with the TCP session
-// machine behind it and its arguments
+// machine behind it and its arguments (fst_atk: the one with the flow-attached monitors in it as well)
 int launch(ppe_ctx *c, const ppe_batch_t *in, const ppe_result_t *out, uint32_t nb, const ppe_cfg_t *cfg,
            hipStream_t s, int slot_set, uint32_t idx_base = 0, const ppe_flowdev *fl = nullptr,
            uint32_t *grid_out = nullptr, uint32_t atk_pbase = 0, const ppe_flow_small_tail *small = nullptr,
            const ppe_ps_kargs *fps = nullptr, bool fps_atk = false, bool small_atk = false,
-           const uint8_t *fatk_pb = nullptr, bool fatk_pb_set = false, const ppe_flow_st_args *fst = nullptr) {
+           const uint8_t *fatk_pb = nullptr, bool fatk_pb_set = false, const ppe_flow_st_args *fst = nullptr,
+           bool fst_atk = false) {
     const int r = c->running;
     const ppe_plan &plan = c->plan[r][fl != nullptr];
     ppe_kargs a;
@@ -768,7 +770,8 @@ int launch(ppe_ctx *c, const ppe_batch_t *in, const ppe_result_t *out, uint32_t 
     }
     rc = track_launch(c, grid, a);
     if (rc != PPE_OK) return rc;
-    rc = fst     ? ppe_launch_flow_stream(&a, small, fst, (int)plan.mode, (void *)s, (void *)e0, (void *)e1)
+    rc = fst_atk ? ppe_launch_flow_stream_attack(&a, small, fst, (int)plan.mode, (void *)s, (void *)e0, (void *)e1)
+         : fst   ? ppe_launch_flow_stream(&a, small, fst, (int)plan.mode, (void *)s, (void *)e0, (void *)e1)
          : fps_atk ? ppe_launch_flow_portscan_attack(&a, small, fps, (int)plan.mode, (void *)s, (void *)e0, (void *)e1)
          : fps   ? ppe_launch_flow_portscan(&a, small, fps, (int)plan.mode, (void *)s, (void *)e0, (void *)e1)
          : small_atk ? ppe_launch_flow_small_attack(&a, small, (int)plan.mode, (void *)s, (void *)e0, (void *)e1)
@@ -2169,10 +2172,12 @@ int ppe_flow_create(ppe_ctx_t *c, uint32_t capacity, uint32_t max_batch) {
     return rc;
 }
 
-// how a flow batch of n packets runs with respect to the TCP session machine (ppe_pick_flow_stream over the context)
+// how a flow batch of n packets runs with respect to the TCP session machine (ppe_pick_flow_stream_monitors over the
+// context: ppe_pick_flow_stream's answer unless ppe_flow_stream_monitors is on)
 static uint32_t flow_stream_pick(const ppe_ctx *c, uint32_t n) {
-    return ppe_pick_flow_stream(n, c->flow && c->flow->stream_on, c->stcp.track, c->stcp.midstream, c->stcp.async_oneside,
-                                c->stcp.reasm, c->ps_flow != nullptr, c->atk_flow != nullptr);
+    return ppe_pick_flow_stream_monitors(n, c->flow && c->flow->stream_on, c->stcp.track, c->stcp.midstream,
+                                         c->stcp.async_oneside, c->stcp.reasm, c->ps_flow != nullptr,
+                                         c->atk_flow != nullptr, c->flow_st_monitors);
 }
 // PPE_FST_REFUSE's error, by its cause
 static int flow_stream_refuse(ppe_ctx *c) {
@@ -2196,7 +2201,10 @@ static int classify_flow_run(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_resu
     if (!out->verdict) return fail(c, PPE_EINVAL, "ppe_classify_flow needs the verdict output");
     // later packets of a tracked flow need the TCP session state machine (stream-tcp.c:3005-3140): that takes
     // ppe_flow_stream_attach, in the one configuration it is built for; refused before anything is touched otherwise
-    const uint32_t fst = flow_stream_pick(c, in ? in->n : 0u);
+    const uint32_t fstm = flow_stream_pick(c, in ? in->n : 0u);
+    // (the session kernel with the monitors in it, ppe_flow_stream_monitors: the session batch's checks and bookkeeping)
+    const bool fst_atk = fstm == PPE_FST_KERNEL_ATK;
+    const uint32_t fst = fst_atk ? (uint32_t)PPE_FST_KERNEL : fstm;
     if (c->stcp.track && fst == PPE_FST_PLAIN)
         return fail(c, PPE_ENOTSUP, "ppe_classify_flow with stream tracking on is not supported");
     if (fst == PPE_FST_REFUSE) return flow_stream_refuse(c);
@@ -2278,7 +2286,7 @@ static int classify_flow_run(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_resu
         const ppe_flow_small_tail tail = {in->len,      out->verdict, out->acl_hit, out->fw_idx, out->drop_idx,
                                           out->tile_cnt, out->part8,  may_overflow ? 1u : 0u, 0u};
         const ppe_flow_st_args sa = {t.arr[t.cur].sess, c->d_stc, t.tuple_scr};
-        rc = launch(c, in, out, 1, cfg, s, 0, 0, &ds, nullptr, 0, &tail, nullptr, false, false, atk_pb, true, &sa);
+        rc = launch(c, in, out, 1, cfg, s, 0, 0, &ds, nullptr, 0, &tail, nullptr, false, false, atk_pb, true, &sa, fst_atk);
         if (rc != PPE_OK) return rc;  // (nothing ran: the table is as it was)
     } else if (fps == PPE_FPS_KERNEL) {
         rc = ps_reserve_keys(pt, in->n);  // (may synchronise and rebuild the detector's table; nothing enqueued yet)
@@ -2351,7 +2359,7 @@ static int classify_flow_run(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_resu
             }
         }
     }
-    t.last_kind = fst == PPE_FST_KERNEL ? 5u : fpc == PPE_FPC_KERNEL ? 3u : fps == PPE_FPS_KERNEL ? 2u : small_atk ? 4u
+    t.last_kind = fst_atk ? 6u : fst == PPE_FST_KERNEL ? 5u : fpc == PPE_FPC_KERNEL ? 3u : fps == PPE_FPS_KERNEL ? 2u : small_atk ? 4u
                   : small ? 1u : 0u;
     t.last_launches = (fst == PPE_FST_KERNEL || fps == PPE_FPS_KERNEL || small || small_atk) ? 1u : 2u;
     t.cum_n[t.batches % FlowTable::kSnapRing] = t.tot_n;
@@ -2386,7 +2394,9 @@ static int classify_flow_host_run(ppe_ctx_t *c, const ppe_batch_t *in, const ppe
     if (out->fw_idx || out->drop_idx || out->tile_cnt || out->part8 || out->packed)
         return fail(c, PPE_EINVAL, "ppe_classify_flow_host takes the per-packet outputs only (no lists, no packed)");
     // ppe_classify_flow's refusals, before anything is touched
-    const uint32_t fst = flow_stream_pick(c, 1u);  // (sessions attached and tracking on: every chunk is a session batch)
+    // (sessions attached and tracking on: every chunk is a session batch, with the monitors in it or without)
+    const uint32_t fstm = flow_stream_pick(c, 1u);
+    const uint32_t fst = fstm == PPE_FST_KERNEL_ATK ? (uint32_t)PPE_FST_KERNEL : fstm;
     if (c->stcp.track && fst == PPE_FST_PLAIN)
         return fail(c, PPE_ENOTSUP, "ppe_classify_flow_host with stream tracking on is not supported");
     if (fst == PPE_FST_REFUSE) return flow_stream_refuse(c);
@@ -2523,6 +2533,21 @@ int ppe_flow_age(ppe_ctx_t *c, uint64_t now_seconds, uint64_t timeout_seconds, u
     k.now = now_seconds;
     k.timeout = timeout_seconds;
     k.nslots = t.nslots;
+    // monitors and sessions together (ppe_flow_stream_monitors): StreamTcp_Flow_ResRelease's syncount_accum decrements
+    // for the flows the age kernel is about to delete, by a pass ahead of it on the same stream
+    if (c->flow_st_monitors == 1u && t.stream_on && t.arr[t.cur].sess && c->atk_flow) {
+        ppe_flow_st_age_kargs ra;
+        std::memset(&ra, 0, sizeof ra);
+        ra.keys = k.f.keys;
+        ra.packed = k.f.packed;
+        ra.sess = t.arr[t.cur].sess;
+        ra.atk_slots = c->atk_flow->d_slots;
+        ra.now = now_seconds;
+        ra.timeout = timeout_seconds;
+        ra.nslots = t.nslots;
+        rc = ppe_launch_flow_stream_age_release(&ra, flow_grid(c, t.nslots, 256u), nullptr);
+        if (rc != 0) return fail(c, PPE_EIO, "flow age launch failed: %s", hipGetErrorString((hipError_t)rc));
+    }
     rc = ppe_launch_flow(PPE_FLOW_K_AGE, &k, flow_grid(c, t.nslots, 256u), nullptr);
     if (rc != 0) return fail(c, PPE_EIO, "flow age launch failed: %s", hipGetErrorString((hipError_t)rc));
     rc = flow_sync_counts(c, after);
@@ -2635,6 +2660,15 @@ int ppe_flow_stream_attach(ppe_ctx_t *c, uint32_t on) {
     return PPE_OK;
 }
 
+// monitors flow-attached and sessions attached on one batch (csrc/ppe_kernels_flow_stream_attack.hip).
+// Like ppe_flow_combine it is the context's: ppe_flow_destroy leaves it
+int ppe_flow_stream_monitors(ppe_ctx_t *c, uint32_t on) {
+    if (!c) return PPE_EINVAL;
+    if (on > 1u) return fail(c, PPE_EINVAL, "ppe_flow_stream_monitors: on must be 0 or 1");
+    c->flow_st_monitors = on;
+    return PPE_OK;
+}
+
 int ppe_flow_stream_dump(ppe_ctx_t *c, ppe_flow_stream_entry_t *entries, uint32_t max, uint32_t *n) {
     if (!c || !n) return PPE_EINVAL;
     if (const int u = flow_usable(c)) return u;
@@ -2665,6 +2699,7 @@ int ppe_flow_stream_dump(ppe_ctx_t *c, ppe_flow_stream_entry_t *entries, uint32_
             e.slot = s;
             e.state = (uint8_t)(w[0] & 0xffu);
             e.flags = (uint16_t)(w[0] >> 8);
+            e.pad = (uint8_t)(w[13] & 3u);  // flow_item_t.input_port (0 unless created under ppe_flow_stream_monitors)
             ppe_stream_side_t *side[2] = {&e.client, &e.server};
             for (int i = 0; i < 2; ++i) {
                 const uint32_t *q = w + 1 + 6 * i;

@@ -413,6 +413,17 @@ struct ppe_flow_st_rehash_kargs {
     uint32_t nslots, dst_gmask;
 };
 
+/* the pass ahead of ppe_flow_age's kernel with monitors and sessions together (csrc/ppe_kernels_flow_stream_attack.hip;
+ * DESIGN.md §5.16): the table's current slot arrays, the age kernel's clock, slot 0 of the monitors' slot array */
+struct ppe_flow_st_age_kargs {
+    const uint32_t *keys;
+    const unsigned long long *packed;
+    const uint32_t *sess;
+    unsigned long long *atk_slots;
+    uint64_t now, timeout;
+    uint32_t nslots, pad;
+};
+
 /* flow-hash steering across GPUs (ppe_steer_partition / ppe_gather_rows / ppe_scatter_rows) */
 #define PPE_STEER_MAX_WORLD 16
 struct ppe_steer_kargs {
@@ -563,6 +574,22 @@ int ppe_launch_flow_stream(const struct ppe_kargs *a, const struct ppe_flow_smal
                            const struct ppe_flow_st_args *st, int mode, void *stream, void *ev_start, void *ev_stop);
 /* the session records' pass behind the flow rehash launch (same file).  Returns hipError_t */
 int ppe_launch_flow_stream_rehash(const struct ppe_flow_st_rehash_kargs *a, uint32_t grid, void *stream);
+/* monitors flow-attached and sessions attached on one batch (ppe_flow_stream_monitors): as ppe_pick_flow_stream, with
+ * PPE_FST_KERNEL_ATK the one-launch kernel with both inside (kind 6: monitors_on 1, monitors flow-attached, no port-scan
+ * table flow-attached, the one configuration, 1 <= n <= PPE_FLOW_ST_MAX).  monitors_on 0: ppe_pick_flow_stream's
+ * answer, whatever else is set; sessions not attached or tracking off: PPE_FST_PLAIN */
+#define PPE_FST_KERNEL_ATK 3u
+uint32_t ppe_pick_flow_stream_monitors(uint32_t n, int attached, uint32_t track, uint32_t midstream,
+                                       uint32_t async_oneside, uint32_t reasm, int ps_flow_attached,
+                                       int atk_flow_attached, uint32_t monitors_on);
+/* the one-launch flow kernel with the session phase and the attack monitors (csrc/ppe_kernels_flow_stream_attack.hip):
+ * as ppe_launch_flow_stream; a->fatk_st and a->fatk_slots must be set.  Returns hipError_t */
+int ppe_launch_flow_stream_attack(const struct ppe_kargs *a, const struct ppe_flow_small_tail *t,
+                                  const struct ppe_flow_st_args *st, int mode, void *stream, void *ev_start,
+                                  void *ev_stop);
+/* StreamTcp_Flow_ResRelease's syncount_accum decrements for the flows the age kernel behind it deletes (same file).
+ * Returns hipError_t */
+int ppe_launch_flow_stream_age_release(const struct ppe_flow_st_age_kargs *a, uint32_t grid, void *stream);
 /* The machine itself on the host, as the kernel compiles it (csrc/ppe_stream_session_dev.h, csrc/ppe_stream_session.cpp):
  * one StreamTcpPacket step on a 16-word session record (the device layout).  pkt = {th_flags, seq, ack, window,
  * payload_len, window-scale shift byte or 0xff without the option, toclient 0/1}; counters (64 words, may be NULL) get

@@ -2886,14 +2886,24 @@ __global__ __launch_bounds__(PPE_FLOW_PS_BLOCK) void ppe_flow_ps_kernel(ppe_flow
 //                stores, nobody else reads it here;
 //   stc[], cslots[]   agent-scope atomic adds, read by nobody in the launch.
 constexpr uint32_t FST_NEW = 1u << 24;
+constexpr uint32_t FST_PORT_SHIFT = 9u;  // ATK: the packet's input port in two free bits of the packet word
+// (csrc/ppe_kernels_flow_stream_attack.hip, PPE_TU_FLOW_ST == 2, builds this text as ppe_flow_st_attack_kernel with ATK:
+// the comment behind the kernel says what that adds)
+#if PPE_TU_FLOW_ST == 2
+#define PPE_FST_KERNEL_NAME ppe_flow_st_attack_kernel
+#else
+#define PPE_FST_KERNEL_NAME ppe_flow_st_kernel
+#endif
 template <int MODE>
-__global__ __launch_bounds__(PPE_FLOW_ST_BLOCK) void ppe_flow_st_kernel(ppe_flow_st_kargs a) {
+__global__ __launch_bounds__(PPE_FLOW_ST_BLOCK) void PPE_FST_KERNEL_NAME(ppe_flow_st_kargs a) {
+    constexpr bool ATK = PPE_TU_FLOW_ST == 2;
     constexpr int BLOCK = PPE_FLOW_ST_BLOCK;
     static_assert(sizeof(ppe_flow_st_kargs) <= 4096u, "HIP's limit for a kernel's explicit arguments");
     static_assert(offsetof(ppe_flow_st_kargs, k) == 0u, "the classify arguments first, at ppe_kargs' own offsets");
     static_assert(PPE_FLOW_ST_MAX <= (uint32_t)BLOCK, "one packet per thread");
     static_assert(PPE_STC__COUNT <= PPE_STC_WORDS && PPE_STC_WORDS <= 64u, "the counter block");
-    classify_body<MODE, PF_HOIST, BLOCK, true>(a.k);
+    if constexpr (ATK) classify_body<MODE, PF_HOIST, BLOCK, true, false, false, false, true>(a.k);
+    else classify_body<MODE, PF_HOIST, BLOCK, true>(a.k);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");
@@ -2914,12 +2924,19 @@ __global__ __launch_bounds__(PPE_FLOW_ST_BLOCK) void ppe_flow_st_kernel(ppe_flow
         f.revoke = a.t.revoke;
         f.fin_wgs = 1u;
         f.cslots = a.k.cslots;
-        flow_finalize_wg<BLOCK, false>(f, 1u, bins, lcnt, part, tail[0], *(unsigned long long *)(tail + 2), tail + 4);
+        if constexpr (ATK) {  // (no argument of their own: the classify arguments carry them)
+            f.atk_slots = a.k.fatk_slots;
+            f.atk_pb = a.k.fatk_pb;
+        }
+        flow_finalize_wg<BLOCK, ATK>(f, 1u, bins, lcnt, part, tail[0], *(unsigned long long *)(tail + 2), tail + 4);
     }
     // ---- session ----
     // LDS: what the classify phase had in front of the image, free behind the barrier
     using LI = Lds<BLOCK, true, 4u * PPE_UPD_OWNERS * (1u + (PPE_UPD_LDS ? PPE_UPD_CAP : 0u))>;
-    static_assert(8u * BLOCK + 4u * (4u * BLOCK + PPE_STC_WORDS + 4u) <= LI::IMGB, "the session arrays fit in front of the image");
+    // (ATK: est[4] behind g, the establishments of this batch per port; the launch's dynamic LDS is the classify
+    // phase's, which these four words do not change)
+    static_assert(8u * BLOCK + 4u * (4u * BLOCK + PPE_STC_WORDS + 4u + (ATK ? 4u : 0u)) <= LI::IMGB,
+                  "the session arrays fit in front of the image");
     unsigned long long *keys = (unsigned long long *)smem;       // [BLOCK] slot << 32 | index, ~0 for the rest
     uint32_t *pf = smem + 2u * BLOCK, *sq = pf + BLOCK, *ak = sq + BLOCK, *wp = ak + BLOCK;  // by packet index
     uint32_t *sc = wp + BLOCK, *g = sc + PPE_STC_WORDS;          // the stream counters; g[0]: drops, g[1]: lost flows
@@ -2927,7 +2944,8 @@ __global__ __launch_bounds__(PPE_FLOW_ST_BLOCK) void ppe_flow_st_kernel(ppe_flow
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     // (the counters lie behind finalize's arrays, which its last loop may still be reading in another wave)
     static_assert(PPE_NBINS + 32u + BLOCK + 8u <= 6u * BLOCK, "the counters lie behind finalize's arrays");
-    if (tid < PPE_STC_WORDS + 4u) sc[tid] = 0u;
+    uint32_t *est = g + 4u;  // ATK: SYN_RECV -> ESTABLISHED steps of this batch, by the completing packet's port
+    if (tid < PPE_STC_WORDS + 4u + (ATK ? 4u : 0u)) sc[tid] = 0u;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");
@@ -2952,6 +2970,8 @@ __global__ __launch_bounds__(PPE_FLOW_ST_BLOCK) void ppe_flow_st_kernel(ppe_flow
             const uint32_t ws = wso ? (uint32_t)th[wso + 2u] : (uint32_t)PPE_SS_NO_WS;
             pf[p] = (uint32_t)th[13] | (((v >> 16) & PPE_F_TOCLIENT) ? 0x100u : 0u) | (ws << 16) |
                     (((v >> 16) & PPE_F_NEWFLOW) ? FST_NEW : 0u);
+            if constexpr (ATK)  // m->input_port: the monitors' port byte of this packet (none: port 0)
+                if (a.k.fatk_pb) pf[p] |= ((uint32_t)a.k.fatk_pb[p] & 3u) << FST_PORT_SHIFT;
             sq[p] = ((uint32_t)th[4] << 24) | ((uint32_t)th[5] << 16) | ((uint32_t)th[6] << 8) | th[7];
             ak[p] = ((uint32_t)th[8] << 24) | ((uint32_t)th[9] << 16) | ((uint32_t)th[10] << 8) | th[11];
             wp[p] = ((uint32_t)th[14] << 8) | th[15] | ((t.w >> 16) << 16);
@@ -2993,6 +3013,7 @@ __global__ __launch_bounds__(PPE_FLOW_ST_BLOCK) void ppe_flow_st_kernel(ppe_flow
             }
             PpeSsn x;
             ppe_ss_unpack(w, x);
+            uint32_t cport = w[13];  // ATK: flow_item_t.input_port (flow.c:139), the creating packet's port
 #pragma unroll 1
             for (uint32_t j = tid; j < np2; ++j) {  // (at most n steps: the group ends where the slot changes)
                 const unsigned long long kj = keys[j];
@@ -3000,10 +3021,18 @@ __global__ __launch_bounds__(PPE_FLOW_ST_BLOCK) void ppe_flow_st_kernel(ppe_flow
                 const uint32_t i = (uint32_t)kj & (BLOCK - 1u);
                 const uint32_t f = pf[i], wl = wp[i];
                 if (f & FST_NEW) x = PpeSsn{};  // FlowAdd gave the flow no session yet: the zero record
+                if constexpr (ATK)
+                    if (f & FST_NEW) cport = (f >> FST_PORT_SHIFT) & 3u;
+                const uint32_t before = x.state;
                 const PpeSsPkt pk = {f & 0xffu, sq[i], ak[i], wl & 0xffffu, wl >> 16, (f >> 16) & 0xffu, (f >> 8) & 1u};
                 sq[i] = ppe_stream_step(x, pk, [&](uint32_t c) { atomicAdd(&sc[c], 1u); });
+                // DP_Attack_SynCountFins (stream-tcp.c:608, :660): the step that completes the handshake, on its packet's port
+                if constexpr (ATK)
+                    if (before == PPE_TCP_SYN_RECV && x.state == PPE_TCP_ESTABLISHED)
+                        atomicAdd(&est[(f >> FST_PORT_SHIFT) & 3u], 1u);
             }
             ppe_ss_pack(x, w);
+            if constexpr (ATK) w[13] = cport;
             rp[0] = make_uint4(w[0], w[1], w[2], w[3]);
             rp[1] = make_uint4(w[4], w[5], w[6], w[7]);
             rp[2] = make_uint4(w[8], w[9], w[10], w[11]);
@@ -3035,8 +3064,73 @@ __global__ __launch_bounds__(PPE_FLOW_ST_BLOCK) void ppe_flow_st_kernel(ppe_flow
     }
     if (tid == 128u && g[1])
         __hip_atomic_fetch_add(&a.k.flow.ctl[PPE_FCTL_ERR], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if constexpr (ATK)  // syncount_accum -= est[port], modulo 2^64 as the reference's cvmx_atomic_add64 (behind the barrier
+                        // above: every walker's LDS adds are in); slot 0 is the slot this workgroup's classify phase flushed into
+        if (tid >= 192u && tid < 196u && est[tid - 192u])
+            __hip_atomic_fetch_add(&a.k.fatk_slots[3u * (tid - 192u) + 2u], 0ull - (unsigned long long)est[tid - 192u],
+                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+#if PPE_TU_FLOW_ST == 2
+// ppe_flow_st_attack_kernel: the same launch with the attack monitors flow-attached as well (csrc/ppe_kernels_flow_stream_attack.hip;
+// ppe_flow_stream_monitors, ppe_pick_flow_stream_monitors): DP_Attack_PacketMonitor, FlowHandlePacket,
+// StreamTcp, as one core running the batch in index order.
+//   classify   the FLOW + ATK body, as the one-launch kernel for small batches runs it (kind 4): a packet a monitor drops
+//              leaves it final and without PPE_F_L4: no lookup, no claim, no record, and neither finalize nor the session
+//              phase sees it (its status is not ACL_FW); the udp_accum / syn_accum counts and the drop totals are flushed
+//              into slot 0 of the monitors' slot array before the phase's last barrier;
+//   finalize   flow_finalize_wg<1024, true>: syncount_accum + k per port for the TCP SYNs that created a flow (flow.c:151-154);
+//   session    the packet word carries the packet's port (bits 9-10).  The walker of a PPE_F_NEWFLOW packet sets word 13 of
+//              the slot's record, flow_item_t.input_port (flow.c:139), after the zeroing; a step that takes the session from
+//              SYN_RECV to ESTABLISHED (the two live StreamTcpPacketSetState(ssn, TCP_ESTABLISHED) sites, stream-tcp.c:609 and
+//              :661, each behind DP_Attack_SynCountFins) adds 1 to the LDS word est[that packet's port];
+//   finish     as without the monitors; one lane per port with est[p] != 0 adds 0 - est[p] to word 3 p + 2 of slot 0.
+// Hang safety: one workgroup; no wait on another workgroup, no spin, no loop the kernel without the monitors does not
+// have (the sort's stages and the walk, at most n steps); the arrive-and-poll pair of finalize is workgroup 0 with itself.
+// Per word, what this adds and how:
+//   port bytes   read-only in the launch: plain loads in all three phases;
+//   est[]        LDS: zeroed before the session phase's first barrier, added to by the walkers (LDS atomics) before the
+//                barrier in front of finish, read behind it;
+//   slot 0's count words   agent-scope atomic adds only (classify's flush, finalize's + k, finish's 0 - k); no load of
+//                them in the launch, the tick kernel of a later launch folds them;
+//   sess word 13   loaded, kept and stored by its slot's walker only, with the rest of the record.
+
+// StreamTcp_Flow_ResRelease (stream-tcp-session.c:61-77, from FlowAgeResRelease, flow.c:413-419) ahead of ppe_flow_age's
+// own kernel on the stream: every TCP flow that kernel is about to delete (the same predicate over the same words: live
+// and idle for more than `timeout`) whose session is still in the handshake (state not NONE and at most SYN_RECV) takes 1
+// off syncount_accum of the flow's port (record word 13).  Grid-stride over the slots; per such slot one 16-B load of
+// the record's first words and word 13; the per-port counts are reduced per wave, one agent-scope atomic add of 0 - k
+// per wave and port into slot 0 of the monitors' slot array.  It stores nothing else: the age kernel behind it turns the
+// slots into tombstones, so a second ppe_flow_age finds none of them.  No wait, no unbounded loop.
+__global__ __launch_bounds__(256) void ppe_flow_st_age_release_kernel(ppe_flow_st_age_kargs a) {
+    uint32_t c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+    for (uint32_t s = blockIdx.x * 256u + threadIdx.x; s < a.nslots; s += gridDim.x * 256u) {
+        if (a.keys[(size_t)PPE_FLOW_SLOT_WORDS * s + 3u] != PPE_FS_LIVE(6u)) continue;
+        const uint64_t l = a.packed[(size_t)PPE_FLOW_REC_WORDS * s + PPE_FLOW_REC_LAST];
+        if (!(a.now > l && a.now - l > a.timeout)) continue;
+        const uint4 r0 = *(const uint4 *)(a.sess + (size_t)PPE_FLOW_SESS_WORDS * s);
+        const uint32_t state = r0.x & 0xffu;
+        if (state == PPE_TCP_NONE || state > PPE_TCP_SYN_RECV) continue;
+        const uint32_t port = a.sess[(size_t)PPE_FLOW_SESS_WORDS * s + 13u] & 3u;
+        c0 += port == 0u;
+        c1 += port == 1u;
+        c2 += port == 2u;
+        c3 += port == 3u;
+    }
+    c0 = wave_sum(c0);
+    c1 = wave_sum(c1);
+    c2 = wave_sum(c2);
+    c3 = wave_sum(c3);
+    if ((threadIdx.x & 63u) == 0) {
+        if (c0) __hip_atomic_fetch_add(&a.atk_slots[2], 0ull - (unsigned long long)c0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (c1) __hip_atomic_fetch_add(&a.atk_slots[5], 0ull - (unsigned long long)c1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (c2) __hip_atomic_fetch_add(&a.atk_slots[8], 0ull - (unsigned long long)c2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (c3) __hip_atomic_fetch_add(&a.atk_slots[11], 0ull - (unsigned long long)c3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+#endif
+
+#if PPE_TU_FLOW_ST == 1
 // Behind a flow rehash: every live TCP flow's session record to the slot its key took in the new slot arrays.  One
 // thread per old slot; the probe is bounded by the new table's groups (the key is there: the rehash launch ahead of this
 // one on the stream inserted every live flow).
@@ -3066,6 +3160,7 @@ __global__ __launch_bounds__(256) void ppe_flow_st_rehash_kernel(ppe_flow_st_reh
         }
     }
 }
+#endif  // PPE_TU_FLOW_ST == 1
 #endif
 
 // FlowTimeOut + FlowAgeTimeoutCB (flow.c:391-467): live flows idle for more than `timeout` become tombstones.
@@ -3375,13 +3470,22 @@ extern "C" int ppe_launch_flow_post_attack(const ppe_flow_kargs *a, uint32_t gri
 // function, finalize over LDS its kernel provides), exporting only the one-launch flow kernel with the TCP session
 // machine behind it over the three image placements of the flow-table plan, at 1024 threads, and the session records'
 // pass behind a rehash
-extern "C" int ppe_launch_flow_stream(const ppe_kargs *a, const ppe_flow_small_tail *t, const ppe_flow_st_args *st,
-                                      int mode, void *stream, void *ev_start, void *ev_stop) {
+// (csrc/ppe_kernels_flow_stream_attack.hip, PPE_TU_FLOW_ST == 2: the same kernel with the attack monitors in its classify
+// phase, the syncount_accum counts in its finalize and session phases, a->fatk_* filled; and the pass ahead of
+// ppe_flow_age's kernel)
+#if PPE_TU_FLOW_ST == 2
+extern "C" int ppe_launch_flow_stream_attack(
+#else
+extern "C" int ppe_launch_flow_stream(
+#endif
+    const ppe_kargs *a, const ppe_flow_small_tail *t, const ppe_flow_st_args *st, int mode, void *stream, void *ev_start,
+    void *ev_stop) {
     const hipStream_t s = (hipStream_t)stream;
     const hipEvent_t e0 = (hipEvent_t)ev_start, e1 = (hipEvent_t)ev_stop;
     if (a->flow.upd_wgs != 0u || a->nbatch != 1u || a->ring || a->batch[0].n == 0u || a->batch[0].n > PPE_FLOW_ST_MAX ||
         a->batch[0].stride < PPE_FLOW_STREAM_MIN_STRIDE || !st || !st->sess || !st->stc || !t->verdict)
         return (int)hipErrorInvalidValue;
+    if (PPE_TU_FLOW_ST == 2 && (!a->fatk_st || !a->fatk_slots)) return (int)hipErrorInvalidValue;
     if (!a->batch[0].tuple && !st->tuple_scratch) return (int)hipErrorInvalidValue;
     ppe_flow_st_kargs k;
     k.k = *a;
@@ -3401,15 +3505,23 @@ extern "C" int ppe_launch_flow_stream(const ppe_kargs *a, const ppe_flow_small_t
     const size_t base = ppe_classify_fixed_lds(PPE_FLOW_ST_BLOCK, PF_HOIST, mode) + ppe_flow_lds_extra();
     const size_t shmem = mode == IMG_GLOBAL ? base : base + (((size_t)a->stage_words * 4u + 1023u) & ~(size_t)1023u);
     const dim3 g(1), b(PPE_FLOW_ST_BLOCK);
-    if (mode == IMG_LDS) hipExtLaunchKernelGGL((ppe_flow_st_kernel<IMG_LDS>), g, b, shmem, s, e0, e1, 0, k);
-    else if (mode == IMG_SPLIT) hipExtLaunchKernelGGL((ppe_flow_st_kernel<IMG_SPLIT>), g, b, shmem, s, e0, e1, 0, k);
-    else hipExtLaunchKernelGGL((ppe_flow_st_kernel<IMG_GLOBAL>), g, b, shmem, s, e0, e1, 0, k);
+    if (mode == IMG_LDS) hipExtLaunchKernelGGL((PPE_FST_KERNEL_NAME<IMG_LDS>), g, b, shmem, s, e0, e1, 0, k);
+    else if (mode == IMG_SPLIT) hipExtLaunchKernelGGL((PPE_FST_KERNEL_NAME<IMG_SPLIT>), g, b, shmem, s, e0, e1, 0, k);
+    else hipExtLaunchKernelGGL((PPE_FST_KERNEL_NAME<IMG_GLOBAL>), g, b, shmem, s, e0, e1, 0, k);
     return (int)hipGetLastError();
 }
+#if PPE_TU_FLOW_ST == 2
+extern "C" int ppe_launch_flow_stream_age_release(const ppe_flow_st_age_kargs *a, uint32_t grid, void *stream) {
+    if (!a->keys || !a->packed || !a->sess || !a->atk_slots) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(ppe_flow_st_age_release_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, *a);
+    return (int)hipGetLastError();
+}
+#else
 extern "C" int ppe_launch_flow_stream_rehash(const ppe_flow_st_rehash_kargs *a, uint32_t grid, void *stream) {
     hipLaunchKernelGGL(ppe_flow_st_rehash_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, *a);
     return (int)hipGetLastError();
 }
+#endif
 #elif defined(PPE_TU_FLOW_SMALL)
 // csrc/ppe_kernels_flow_small.hip: this file again, exporting only the one-launch kernel for small flow batches over
 // the three image placements of the flow-table plan, at 1024 threads

@@ -229,7 +229,9 @@ class Engine:
         """ppe_flow_launch_info: (kind, launches) of the last flow batch: (1, 1) the one-launch kernel, (2, 1) the
         one-launch kernel with the port-scan detector inside, (3, 1) that kernel with the flow-attached monitors in it as
         well (flow_combine), (4, 1) the one-launch kernel with the flow-attached monitors in it (chunks of
-        classify_flow_host_ports only), (0, 2) the two launches, (0, 0) before the first."""
+        classify_flow_host_ports only), (5, 1) the one-launch kernel with the TCP session machine behind it
+        (flow_stream), (6, 1) that kernel with the flow-attached monitors in it as well (flow_stream_monitors), (0, 2)
+        the two launches, (0, 0) before the first."""
         k, n = C.c_uint32(9), C.c_uint32(9)
         self._check(self.lib.ppe_flow_launch_info(self.ctx, C.byref(k), C.byref(n)), "ppe_flow_launch_info")
         return k.value, n.value
@@ -321,6 +323,13 @@ class Engine:
         (with stream_tcp(track=1, reasm=0); flow_launch_info (5, 1)); every session record is zeroed.  0: the plain
         kernels again.  Needs a flow table."""
         self._check(self.lib.ppe_flow_stream_attach(self.ctx, int(on)), "ppe_flow_stream_attach")
+
+    def flow_stream_monitors(self, on: int) -> None:
+        """ppe_flow_stream_monitors: 1, a flow batch with sessions attached and attack monitors flow-attached runs the
+        monitors, the table and the sessions in one launch (flow_launch_info (6, 1)), and syncount_accum takes its
+        decrements (a completed handshake, a flow aged out in its handshake); 0 (a new context): such a batch is
+        refused."""
+        self._check(self.lib.ppe_flow_stream_monitors(self.ctx, int(on)), "ppe_flow_stream_monitors")
 
     def flow_stream_max(self) -> int:
         """ppe_flow_stream_max: the packets one device flow batch takes with sessions attached."""
