@@ -483,7 +483,9 @@ int ppe_classify_flow_host_ports(ppe_ctx_t *ctx, const ppe_batch_t *in, const pp
  * flow-attached attack monitors in it as well, ppe_flow_combine), 4 and 1 (the one-launch kernel with the
  * flow-attached monitors in it: chunks of ppe_classify_flow_host_ports only), or 0 and 2; 0 and 0 before the first
  * batch; 5 and 1: the one-launch kernel with the TCP session machine behind it (ppe_flow_stream_attach); 6 and 1:
- * that kernel with the flow-attached monitors in it as well (ppe_flow_stream_monitors).  NULL arguments: PPE_EINVAL. */
+ * that kernel with the flow-attached monitors in it as well (ppe_flow_stream_monitors); 7 and 1: the one-launch kernel
+ * with the port-scan detector inside and the TCP session machine behind it (ppe_flow_stream_portscan); 8 and 1: that
+ * kernel with the flow-attached monitors in it as well.  NULL arguments: PPE_EINVAL. */
 int  ppe_flow_launch_info(ppe_ctx_t *ctx, uint32_t *kind, uint32_t *launches);
 /* FlowAgeTimeoutCB: delete flows with now > last_seen && now - last_seen > timeout_seconds; *deleted = count
  * (may be NULL).  Synchronises. */
@@ -518,8 +520,8 @@ int  ppe_flow_dump(ppe_ctx_t *ctx, ppe_flow_entry_t *entries, uint32_t max, uint
  *   rehash moves the records with their flows.  Not kept: ra_app_base_seq, ra_raw_base_seq, last_ts, last_pkt_ts,
  *   os_policy, the segment lists.
  * Refused before anything is touched: attached with track 1 and any of reasm, midstream, async_oneside 1
- * (PPE_ENOTSUP); a port-scan table flow-attached at the same time, or monitors flow-attached unless
- * ppe_flow_stream_monitors is on (PPE_ENOTSUP); a device batch of more
+ * (PPE_ENOTSUP); a port-scan table flow-attached at the same time unless ppe_flow_stream_portscan is on, or monitors
+ * flow-attached unless ppe_flow_stream_monitors is on (PPE_ENOTSUP); a device batch of more
  * than ppe_flow_stream_max() packets (PPE_ENOTSUP; ppe_classify_flow_host takes host batches of any size in chunks
  * of at most that); a header stride under 144 B (PPE_EINVAL: neither PPE_ST_WINDOW_PUNT nor PPE_TUPLE_OPT_PAST may
  * stand between a SYN and its window scale); attach without a flow table (PPE_EINVAL).  Attached with track 0 the
@@ -564,9 +566,43 @@ int  ppe_flow_stream_dump(ppe_ctx_t *ctx, ppe_flow_stream_entry_t *entries, uint
  * ppe_classify_flow_host_ports runs host batches of any size under the same conditions (chunks of at most
  * ppe_flow_stream_max(), each one launch with its slice of `ports`); ppe_classify_flow_host keeps refusing monitors
  * flow-attached.  Still refused before anything is touched: the switch off, a port-scan table flow-attached as well
- * (whatever its able), a larger device batch, reasm / midstream / async_oneside 1 (PPE_ENOTSUP); a stride under 144 B
- * (PPE_EINVAL).  With the switch on but only one of the two attached, or track 0, nothing changes. */
+ * (whatever its able; ppe_flow_stream_portscan, below, lifts this), a larger device batch, reasm / midstream /
+ * async_oneside 1 (PPE_ENOTSUP); a stride under 144 B (PPE_EINVAL).  With the switch on but only one of the two attached, or track 0, nothing changes. */
 int  ppe_flow_stream_monitors(ppe_ctx_t *ctx, uint32_t on);
+/* ---- A port-scan table flow-attached and sessions attached on one batch: the reference's default pipeline ----
+ * Decode -> attack monitors -> FlowHandlePacket -> FlowFind | miss -> syn_check -> PortScan_Detect -> DP_Acl_Lookup ->
+ * FlowAdd -> FlowUpdate -> StreamTcp (flow.c:196-243, :271-320), with portscan_able 1 and stream_tcp_track_enable 1.
+ * 0 (a new context): as before, the two together are refused, and every call, refusal, kernel, launch kind and result
+ * is what it was.  on > 1: PPE_EINVAL.  The context's, like ppe_flow_combine and ppe_flow_stream_monitors:
+ * ppe_flow_destroy leaves it; no synchronisation.
+ * 1, with sessions attached, ppe_stream_tcp_set holding {1,0,0,0} and a table attached with ppe_flow_portscan_attach whose
+ * able is 1: ppe_classify_flow takes a batch of 1 <= n <= min(ppe_flow_portscan_max(), ppe_flow_stream_max()) packets
+ * (stride >= PPE_FLOW_STREAM_MIN_STRIDE) in one launch.  No monitors flow-attached: ppe_flow_launch_info kind 7.  Monitors
+ * flow-attached as well: ppe_flow_combine and ppe_flow_stream_monitors must both be 1 (each pair has been opted into), and
+ * the kind is 8; with either off the call is refused as before.  Exactly one core running the batch in index order:
+ *   1. the monitors, if attached, as under ppe_flow_combine (1): a packet they drop reaches neither table nor the
+ *      detector nor its session;
+ *   2. the survivors take ppe_flow_portscan_attach's path unchanged: a packet that finds its flow is never at the
+ *      detector; the rest take syn_check, PortScan_Detect, then PPE_ST_PORTSCAN_DROP, or the ACL and FlowAdd or
+ *      PPE_ST_FLOW_NOMEM;
+ *   3. every packet that ends PPE_ST_ACL_FW with PPE_F_FLOW | PPE_F_TCP steps its flow's session exactly as under
+ *      ppe_flow_stream_attach, a PPE_F_NEWFLOW packet from the zero record.  A packet that ends PPE_ST_PORTSCAN_DROP,
+ *      PPE_ST_FLOW_TCP_NO_SYN_FIRST, PPE_ST_ACL_DROP or PPE_ST_FLOW_NOMEM has no flow: it takes no step and counts in no
+ *      stream counter.  A stream drop (status 20-23, or 29 with the reason bits; action DROP; OUT_FW handed to OUT_DROP)
+ *      keeps the flow, the detector's record and every flag: StreamTcp runs behind FlowAdd and FlowUpdate and its
+ *      verdict feeds nothing back (flow.c:304-319);
+ *   4. kind 8: syncount_accum takes +1 on the packet's port for a TCP SYN that ends with PPE_F_NEWFLOW and -1 on the
+ *      completing packet's port for SYN_RECV -> ESTABLISHED, as under ppe_flow_stream_monitors; session record word 13 is
+ *      the creating packet's port, and ppe_flow_age's release pass runs under its condition, so a scan's half-open flows
+ *      give their +1 back when they age out.  Kind 7 stores 0 there.
+ * 1 with able != 1: the detector is off, so the batch runs as if no table were flow-attached (kinds 5 / 6, their results
+ * byte for byte).  1 with only the sessions or only the table attached, or track 0: nothing changes.
+ * ppe_classify_flow_host runs host batches of any size as kind 7 per chunk (a multiple of 64, at most the smaller of the
+ * two maxima and of both tables' max_batch; `ts` per chunk), ppe_classify_flow_host_ports as kind 8 per chunk with its
+ * slice of `ports`: one core's run of the whole batch whatever the chunk (only the flow table's tombstone count may
+ * differ).  Refused before anything is touched: a larger device batch, reasm / midstream / async_oneside 1
+ * (PPE_ENOTSUP); a stride under 144 B, n above the port-scan table's max_batch (PPE_EINVAL). */
+int  ppe_flow_stream_portscan(ppe_ctx_t *ctx, uint32_t on);
 /* struct tcpstream_track_stat (decode-statistic.h:118-179), every field in the reference's order; the session path
  * counts here (the stateless path keeps feeding ppe_stream_counters_t) */
 enum ppe_stream_track_counter {

@@ -409,4 +409,29 @@ uint32_t ppe_pick_flow_stream_monitors(uint32_t n, int attached, uint32_t track,
     return r == PPE_FST_KERNEL ? PPE_FST_KERNEL_ATK : r;
 }
 
+// the same with the context's switch for the port-scan detector and sessions on one batch (ppe_flow_stream_portscan;
+// csrc/ppe_kernels_flow_portscan_stream.hip, csrc/ppe_kernels_flow_portscan_attack_stream.hip): off, or no table
+// flow-attached, ppe_pick_flow_stream_monitors' answer.  On with the detector off (portscan_able != 1, dp_portscan.c:238:
+// PortScan_Detect returns at once), the answer as if no table were flow-attached.  On with the detector on: the session
+// machine's own conditions first (not attached or tracking off: PLAIN, the detector's planners decide; a configuration
+// it is not built for, or a batch past either kernel's workgroup: REFUSE); then the detector kernel with the session
+// phase behind it, with the monitors in it only for a context that opted into both pairs (ppe_flow_combine for
+// monitors + detector, ppe_flow_stream_monitors for monitors + sessions), else refused as it always was
+uint32_t ppe_pick_flow_stream_portscan(uint32_t n, int attached, uint32_t track, uint32_t midstream,
+                                       uint32_t async_oneside, uint32_t reasm, int ps_flow_attached,
+                                       int atk_flow_attached, uint32_t monitors_on, uint32_t able, uint32_t portscan_on,
+                                       uint32_t combine_on) {
+    if (portscan_on != 1u || !ps_flow_attached)
+        return ppe_pick_flow_stream_monitors(n, attached, track, midstream, async_oneside, reasm, ps_flow_attached,
+                                             atk_flow_attached, monitors_on);
+    if (able != 1u)
+        return ppe_pick_flow_stream_monitors(n, attached, track, midstream, async_oneside, reasm, 0, atk_flow_attached,
+                                             monitors_on);
+    const uint32_t r = ppe_pick_flow_stream(n, attached, track, midstream, async_oneside, reasm, 0, 0);
+    if (r != PPE_FST_KERNEL) return r;
+    if (n > PPE_FLOW_PS_MAX) return PPE_FST_REFUSE;
+    if (!atk_flow_attached) return PPE_FST_KERNEL_PS;
+    return (monitors_on == 1u && combine_on == 1u) ? PPE_FST_KERNEL_PS_ATK : PPE_FST_REFUSE;
+}
+
 }  // extern "C"

@@ -224,6 +224,7 @@ struct ppe_ctx {
     ppe_attack *atk_flow = nullptr;    // ppe_flow_attack_attach: ppe_classify_flow's monitors (never the same object as atk)
     uint32_t flow_combine = 0;         // ppe_flow_combine: ps_flow (able 1) and atk_flow on one batch, in one launch
     uint32_t flow_st_monitors = 0;     // ppe_flow_stream_monitors: atk_flow and the sessions on one batch, in one launch
+    uint32_t flow_st_portscan = 0;     // ppe_flow_stream_portscan: ps_flow (able 1) and the sessions on one batch, in one launch
     unsigned long long *d_stc = nullptr;  // the session path's counter block (PPE_STC_WORDS), from the first attach on
     FlowTable *flow = nullptr;  // ppe_flow_create
     LookupStage lk;             // ppe_acl_lookup_host
@@ -680,7 +681,8 @@ int ps_prepass(ppe_ctx *c, const ppe_batch_t *in, uint32_t nb, const ppe_cfg_t *
 // (fps_atk: the one with the flow-attached monitors in it as well); small_atk: the one-launch kernel of small with
 // the flow-attached monitors in it; fatk_pb_set: the flow-attached monitors read the port bytes fatk_pb (device
 // pointer or NULL) instead of the sticky table's entry 0; fst (with small): the one-launch kernel with the TCP session
-// machine behind it and its arguments (fst_atk: the one with the flow-attached monitors in it as well)
+// machine behind it and its arguments (fst_atk: the one with the flow-attached monitors in it as well); fps and fst
+// together: the detector kernel with the session phase behind it (fst_atk: with the monitors in it as well)
 int launch(ppe_ctx *c, const ppe_batch_t *in, const ppe_result_t *out, uint32_t nb, const ppe_cfg_t *cfg,
            hipStream_t s, int slot_set, uint32_t idx_base = 0, const ppe_flowdev *fl = nullptr,
            uint32_t *grid_out = nullptr, uint32_t atk_pbase = 0, const ppe_flow_small_tail *small = nullptr,
@@ -770,7 +772,10 @@ int launch(ppe_ctx *c, const ppe_batch_t *in, const ppe_result_t *out, uint32_t 
     }
     rc = track_launch(c, grid, a);
     if (rc != PPE_OK) return rc;
-    rc = fst_atk ? ppe_launch_flow_stream_attack(&a, small, fst, (int)plan.mode, (void *)s, (void *)e0, (void *)e1)
+    rc = (fps && fst && fst_atk)
+             ? ppe_launch_flow_stream_portscan_attack(&a, small, fps, fst, (int)plan.mode, (void *)s, (void *)e0, (void *)e1)
+         : (fps && fst) ? ppe_launch_flow_stream_portscan(&a, small, fps, fst, (int)plan.mode, (void *)s, (void *)e0, (void *)e1)
+         : fst_atk ? ppe_launch_flow_stream_attack(&a, small, fst, (int)plan.mode, (void *)s, (void *)e0, (void *)e1)
          : fst   ? ppe_launch_flow_stream(&a, small, fst, (int)plan.mode, (void *)s, (void *)e0, (void *)e1)
          : fps_atk ? ppe_launch_flow_portscan_attack(&a, small, fps, (int)plan.mode, (void *)s, (void *)e0, (void *)e1)
          : fps   ? ppe_launch_flow_portscan(&a, small, fps, (int)plan.mode, (void *)s, (void *)e0, (void *)e1)
@@ -2172,21 +2177,31 @@ int ppe_flow_create(ppe_ctx_t *c, uint32_t capacity, uint32_t max_batch) {
     return rc;
 }
 
-// how a flow batch of n packets runs with respect to the TCP session machine (ppe_pick_flow_stream_monitors over the
-// context: ppe_pick_flow_stream's answer unless ppe_flow_stream_monitors is on)
+// how a flow batch of n packets runs with respect to the TCP session machine (ppe_pick_flow_stream_portscan over the
+// context: ppe_pick_flow_stream's answer unless ppe_flow_stream_monitors or ppe_flow_stream_portscan is on)
 static uint32_t flow_stream_pick(const ppe_ctx *c, uint32_t n) {
-    return ppe_pick_flow_stream_monitors(n, c->flow && c->flow->stream_on, c->stcp.track, c->stcp.midstream,
+    return ppe_pick_flow_stream_portscan(n, c->flow && c->flow->stream_on, c->stcp.track, c->stcp.midstream,
                                          c->stcp.async_oneside, c->stcp.reasm, c->ps_flow != nullptr,
-                                         c->atk_flow != nullptr, c->flow_st_monitors);
+                                         c->atk_flow != nullptr, c->flow_st_monitors,
+                                         c->ps_flow ? c->ps_flow->cfg.able : 0u, c->flow_st_portscan, c->flow_combine);
 }
+// (the planner's answers that are the session kernel with more inside: the session batch's checks and bookkeeping)
+static bool fst_has_ps(uint32_t r) { return r == PPE_FST_KERNEL_PS || r == PPE_FST_KERNEL_PS_ATK; }
+static bool fst_has_atk(uint32_t r) { return r == PPE_FST_KERNEL_ATK || r == PPE_FST_KERNEL_PS_ATK; }
 // PPE_FST_REFUSE's error, by its cause
 static int flow_stream_refuse(ppe_ctx *c) {
     if (c->stcp.midstream || c->stcp.async_oneside || c->stcp.reasm)
         return fail(c, PPE_ENOTSUP, "TCP sessions on the flow path are built for midstream 0, async_oneside 0, reasm 0 "
                                     "(ppe_stream_tcp_set)");
-    if (c->ps_flow || c->atk_flow)
+    // (ppe_flow_stream_portscan on and the combination itself runs, at one packet: the batch is what is refused)
+    const bool size_only = c->flow_st_portscan == 1u && c->ps_flow && flow_stream_pick(c, 1u) != PPE_FST_REFUSE;
+    if ((c->ps_flow || c->atk_flow) && !size_only)
         return fail(c, PPE_ENOTSUP, "TCP sessions on the flow path with a port-scan table or attack monitors flow-attached "
                                     "are not supported");
+    // (with monitors flow-attached ppe_classify_flow_host is itself refused: the ports call is the one that chunks)
+    if (size_only && c->atk_flow)
+        return fail(c, PPE_ENOTSUP, "ppe_classify_flow with TCP sessions takes at most %u packets per batch "
+                                    "(ppe_flow_stream_max; ppe_classify_flow_host_ports chunks larger ones)", PPE_FLOW_ST_MAX);
     return fail(c, PPE_ENOTSUP, "ppe_classify_flow with TCP sessions takes at most %u packets per batch "
                                 "(ppe_flow_stream_max; ppe_classify_flow_host chunks larger ones)", PPE_FLOW_ST_MAX);
 }
@@ -2202,9 +2217,10 @@ static int classify_flow_run(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_resu
     // later packets of a tracked flow need the TCP session state machine (stream-tcp.c:3005-3140): that takes
     // ppe_flow_stream_attach, in the one configuration it is built for; refused before anything is touched otherwise
     const uint32_t fstm = flow_stream_pick(c, in ? in->n : 0u);
-    // (the session kernel with the monitors in it, ppe_flow_stream_monitors: the session batch's checks and bookkeeping)
-    const bool fst_atk = fstm == PPE_FST_KERNEL_ATK;
-    const uint32_t fst = fst_atk ? (uint32_t)PPE_FST_KERNEL : fstm;
+    // (the session kernel with the monitors in it, ppe_flow_stream_monitors, with the detector in it,
+    // ppe_flow_stream_portscan, or both: the session batch's checks and bookkeeping)
+    const bool fst_atk = fst_has_atk(fstm), fst_ps = fst_has_ps(fstm);
+    const uint32_t fst = (fst_atk || fst_ps) ? (uint32_t)PPE_FST_KERNEL : fstm;
     if (c->stcp.track && fst == PPE_FST_PLAIN)
         return fail(c, PPE_ENOTSUP, "ppe_classify_flow with stream tracking on is not supported");
     if (fst == PPE_FST_REFUSE) return flow_stream_refuse(c);
@@ -2279,7 +2295,28 @@ static int classify_flow_run(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_resu
     const bool small_atk = fps != PPE_FPS_KERNEL &&
                            ppe_pick_flow_small_attack(in->n, t.small_allowed && __atomic_load_n(&g_fail_post, __ATOMIC_RELAXED) == 0u,
                                                       c->atk_flow != nullptr, ports_call) != 0u;
-    if (fst == PPE_FST_KERNEL) {
+    if (fst_ps) {
+        // FlowHandlePacket with PortScan_Detect on its misses, then StreamTcp: one launch of one workgroup (kinds 7 / 8)
+        rc = ps_reserve_keys(pt, in->n);  // (may synchronise and rebuild the detector's table; nothing enqueued yet)
+        if (rc != PPE_OK) return rc;
+        ppe_ps_kargs pa;
+        ps_table_args(*pt, pa);
+        pa.ts = in->ts;
+        pa.ts_default = cfg ? cfg->now_seconds : 0u;
+        pa.n = in->n;
+        pa.now_cycles = pt->now_cycles;
+        pa.now_seconds = pt->now_seconds;
+        pa.freq = pt->cfg.exception_freq;
+        pa.hold_seconds = pt->cfg.hold_seconds;
+        pa.action = pt->cfg.action;
+        ppe_flowdev ds = d;
+        ds.upd_wgs = 0;
+        const ppe_flow_small_tail tail = {in->len,      out->verdict, out->acl_hit, out->fw_idx, out->drop_idx,
+                                          out->tile_cnt, out->part8,  0u,           0u};
+        const ppe_flow_st_args sa = {t.arr[t.cur].sess, c->d_stc, t.tuple_scr};
+        rc = launch(c, in, out, 1, cfg, s, 0, 0, &ds, nullptr, 0, &tail, &pa, false, false, atk_pb, true, &sa, fst_atk);
+        if (rc != PPE_OK) return rc;  // (nothing ran: both tables are as they were)
+    } else if (fst == PPE_FST_KERNEL) {
         // FlowHandlePacket, then StreamTcp for the TCP packets that have a flow: one launch of one workgroup
         ppe_flowdev ds = d;
         ds.upd_wgs = 0;
@@ -2359,7 +2396,7 @@ static int classify_flow_run(ppe_ctx_t *c, const ppe_batch_t *in, const ppe_resu
             }
         }
     }
-    t.last_kind = fst_atk ? 6u : fst == PPE_FST_KERNEL ? 5u : fpc == PPE_FPC_KERNEL ? 3u : fps == PPE_FPS_KERNEL ? 2u : small_atk ? 4u
+    t.last_kind = fst_ps ? (fst_atk ? 8u : 7u) : fst_atk ? 6u : fst == PPE_FST_KERNEL ? 5u : fpc == PPE_FPC_KERNEL ? 3u : fps == PPE_FPS_KERNEL ? 2u : small_atk ? 4u
                   : small ? 1u : 0u;
     t.last_launches = (fst == PPE_FST_KERNEL || fps == PPE_FPS_KERNEL || small || small_atk) ? 1u : 2u;
     t.cum_n[t.batches % FlowTable::kSnapRing] = t.tot_n;
@@ -2396,7 +2433,7 @@ static int classify_flow_host_run(ppe_ctx_t *c, const ppe_batch_t *in, const ppe
     // ppe_classify_flow's refusals, before anything is touched
     // (sessions attached and tracking on: every chunk is a session batch, with the monitors in it or without)
     const uint32_t fstm = flow_stream_pick(c, 1u);
-    const uint32_t fst = fstm == PPE_FST_KERNEL_ATK ? (uint32_t)PPE_FST_KERNEL : fstm;
+    const uint32_t fst = (fst_has_atk(fstm) || fst_has_ps(fstm)) ? (uint32_t)PPE_FST_KERNEL : fstm;
     if (c->stcp.track && fst == PPE_FST_PLAIN)
         return fail(c, PPE_ENOTSUP, "ppe_classify_flow_host with stream tracking on is not supported");
     if (fst == PPE_FST_REFUSE) return flow_stream_refuse(c);
@@ -2419,7 +2456,10 @@ static int classify_flow_host_run(ppe_ctx_t *c, const ppe_batch_t *in, const ppe
     if (fst == PPE_FST_KERNEL && in->stride < PPE_FLOW_STREAM_MIN_STRIDE)
         return fail(c, PPE_EINVAL, "ppe_classify_flow_host with TCP sessions needs a header stride of at least %u B",
                     PPE_FLOW_STREAM_MIN_STRIDE);
-    const uint32_t bmax = fst == PPE_FST_KERNEL ? std::min(c->flow->max_batch, PPE_FLOW_ST_MAX)
+    // (both: chunks of at most the smaller of the two, inside both tables' max_batch)
+    const uint32_t bmax = fst_has_ps(fstm) ? std::min(std::min(c->flow->max_batch, c->ps_flow->cfg.max_batch),
+                                                      std::min(PPE_FLOW_ST_MAX, PPE_FLOW_PS_MAX))
+                          : fst == PPE_FST_KERNEL ? std::min(c->flow->max_batch, PPE_FLOW_ST_MAX)
                           : fps ? std::min(c->flow->max_batch, std::min(c->ps_flow->cfg.max_batch, PPE_FLOW_PS_MAX))
                                 : c->flow->max_batch;
     const uint32_t cmax = bmax & ~63u;
@@ -2666,6 +2706,16 @@ int ppe_flow_stream_monitors(ppe_ctx_t *c, uint32_t on) {
     if (!c) return PPE_EINVAL;
     if (on > 1u) return fail(c, PPE_EINVAL, "ppe_flow_stream_monitors: on must be 0 or 1");
     c->flow_st_monitors = on;
+    return PPE_OK;
+}
+
+// a port-scan table flow-attached (able 1) and sessions attached on one batch (csrc/ppe_kernels_flow_portscan_stream.hip,
+// csrc/ppe_kernels_flow_portscan_attack_stream.hip).  The context's, like ppe_flow_combine and
+// ppe_flow_stream_monitors: ppe_flow_destroy leaves it
+int ppe_flow_stream_portscan(ppe_ctx_t *c, uint32_t on) {
+    if (!c) return PPE_EINVAL;
+    if (on > 1u) return fail(c, PPE_EINVAL, "ppe_flow_stream_portscan: on must be 0 or 1");
+    c->flow_st_portscan = on;
     return PPE_OK;
 }
 

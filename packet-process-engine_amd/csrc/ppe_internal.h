@@ -405,6 +405,18 @@ struct ppe_flow_st_args {
     unsigned long long *stc;
     uint32_t *tuple_scratch;      /* PPE_FLOW_ST_MAX x 4 words: the batch's tuples when the caller asks for none */
 };
+/* the detector kernel's arguments, then the session kernel's (csrc/ppe_kernels_flow_portscan_stream.hip):
+ * ppe_flow_ps_kargs' three members at their offsets, the list pointers NULL in k and t as in ppe_flow_st_kargs, then the
+ * lists, the session records, the counter block under ppe_flow_st_kargs' names */
+struct ppe_flow_ps_st_kargs {
+    struct ppe_kargs k;
+    struct ppe_flow_small_tail t;
+    struct ppe_ps_kargs ps;
+    uint32_t *fw_idx, *drop_idx, *tile_cnt;
+    uint8_t *part8;
+    uint32_t *sess;
+    unsigned long long *stc;
+};
 /* the pass behind a rehash: every live flow's record from the old slot arrays to the slot its key took in the new */
 struct ppe_flow_st_rehash_kargs {
     const uint32_t *src_keys, *dst_keys;
@@ -590,6 +602,30 @@ int ppe_launch_flow_stream_attack(const struct ppe_kargs *a, const struct ppe_fl
 /* StreamTcp_Flow_ResRelease's syncount_accum decrements for the flows the age kernel behind it deletes (same file).
  * Returns hipError_t */
 int ppe_launch_flow_stream_age_release(const struct ppe_flow_st_age_kargs *a, uint32_t grid, void *stream);
+/* the port-scan detector and the sessions on one batch (ppe_flow_stream_portscan): everything
+ * ppe_pick_flow_stream_monitors takes, the table's portscan_able, the new switch and ppe_flow_combine's.  portscan_on 0,
+ * or no table flow-attached: ppe_pick_flow_stream_monitors' answer.  On, able != 1: the detector is off, so its answer
+ * as if no table were flow-attached (kinds 5 / 6).  On, able 1: sessions not attached or tracking off PPE_FST_PLAIN (the
+ * detector's own planners decide); the one configuration and 1 <= n <= min(PPE_FLOW_PS_MAX, PPE_FLOW_ST_MAX):
+ * PPE_FST_KERNEL_PS without monitors flow-attached (kind 7), PPE_FST_KERNEL_PS_ATK with them when monitors_on and
+ * combine_on are both 1 (kind 8); everything else PPE_FST_REFUSE */
+#define PPE_FST_KERNEL_PS 4u
+#define PPE_FST_KERNEL_PS_ATK 5u
+uint32_t ppe_pick_flow_stream_portscan(uint32_t n, int attached, uint32_t track, uint32_t midstream,
+                                       uint32_t async_oneside, uint32_t reasm, int ps_flow_attached,
+                                       int atk_flow_attached, uint32_t monitors_on, uint32_t able, uint32_t portscan_on,
+                                       uint32_t combine_on);
+/* the one-launch flow kernel with the detector inside and the session phase behind it
+ * (csrc/ppe_kernels_flow_portscan_stream.hip): as ppe_launch_flow_portscan and ppe_launch_flow_stream together, 1 <=
+ * a->batch[0].n <= min(PPE_FLOW_PS_MAX, PPE_FLOW_ST_MAX), a->batch[0].stride >= 144.  Returns hipError_t */
+int ppe_launch_flow_stream_portscan(const struct ppe_kargs *a, const struct ppe_flow_small_tail *t,
+                                    const struct ppe_ps_kargs *ps, const struct ppe_flow_st_args *st, int mode,
+                                    void *stream, void *ev_start, void *ev_stop);
+/* the same with the attack monitors in it (csrc/ppe_kernels_flow_portscan_attack_stream.hip): a->fatk_st and
+ * a->fatk_slots must be set.  Returns hipError_t */
+int ppe_launch_flow_stream_portscan_attack(const struct ppe_kargs *a, const struct ppe_flow_small_tail *t,
+                                           const struct ppe_ps_kargs *ps, const struct ppe_flow_st_args *st, int mode,
+                                           void *stream, void *ev_start, void *ev_stop);
 /* The machine itself on the host, as the kernel compiles it (csrc/ppe_stream_session_dev.h, csrc/ppe_stream_session.cpp):
  * one StreamTcpPacket step on a 16-word session record (the device layout).  pkt = {th_flags, seq, ack, window,
  * payload_len, window-scale shift byte or 0xff without the option, toclient 0/1}; counters (64 words, may be NULL) get

@@ -2575,8 +2575,24 @@ constexpr uint32_t FPS_NOREC = 0x20000u, FPS_STEPPED = 0x40000u;  // a source's 
 // pending, no claim, no candidate, and the rounds run over the survivors unchanged; finalize counts the TCP SYN creators
 // per port (ballots, one LDS add per non-empty port and wave) and adds them into words 3 port + 2 (syncount_accum) of
 // slot 0 of the monitors' slot array, the slot the classify phase of this one workgroup flushed its own counts into.
+// (csrc/ppe_kernels_flow_portscan_stream.hip and csrc/ppe_kernels_flow_portscan_attack_stream.hip, PPE_TU_FLOW_PS_ST, build
+// this text as ppe_flow_ps_st_kernel with the TCP session machine behind it: the comment behind the kernel says what
+// that changes.  Every line they add or leave out stands between #if defined(PPE_TU_FLOW_PS_ST) and its #endif, so the
+// units without the macro compile the tokens they always did)
+#if defined(PPE_TU_FLOW_PS_ST)
+#include "ppe_stream_session_dev.h"
+constexpr uint32_t FST_NEW = 1u << 24;   // as in front of ppe_flow_st_kernel, which this unit does not compile
+constexpr uint32_t FST_PORT_SHIFT = 9u;
+template <int MODE, bool ATK = false>
+__global__ __launch_bounds__(PPE_FLOW_PS_BLOCK) void ppe_flow_ps_st_kernel(ppe_flow_ps_st_kargs a) {
+    static_assert(sizeof(ppe_flow_ps_st_kargs) <= 4096u, "HIP's limit for a kernel's explicit arguments");
+    static_assert(offsetof(ppe_flow_ps_st_kargs, k) == 0u, "the classify arguments first, at ppe_kargs' own offsets");
+    static_assert(PPE_FLOW_ST_MAX == PPE_FLOW_PS_MAX && PPE_FLOW_ST_BLOCK == PPE_FLOW_PS_BLOCK, "one packet per thread in both");
+    static_assert(PPE_STC__COUNT <= PPE_STC_WORDS && PPE_STC_WORDS <= 64u, "the counter block");
+#else
 template <int MODE, bool ATK = false>
 __global__ __launch_bounds__(PPE_FLOW_PS_BLOCK) void ppe_flow_ps_kernel(ppe_flow_ps_kargs a) {
+#endif
     constexpr int BLOCK = PPE_FLOW_PS_BLOCK;
     static_assert(sizeof(ppe_flow_ps_kargs) <= 4096u, "HIP's limit for a kernel's explicit arguments");
     static_assert(offsetof(ppe_flow_ps_kargs, k) == 0u, "the classify arguments first, at ppe_kargs' own offsets");
@@ -2587,6 +2603,9 @@ __global__ __launch_bounds__(PPE_FLOW_PS_BLOCK) void ppe_flow_ps_kernel(ppe_flow
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");
     // LDS: what the classify phase had in front of the image (key slots, bins, owner buckets), free behind the barrier
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+#if defined(PPE_TU_FLOW_PS_ST)
+    {  // the detector kernel's phases in a scope of their own: the session phase behind them names its own tid, n, v, g, ...
+#endif
     using L = Lds<BLOCK, true, 4u * PPE_UPD_OWNERS * (1u + (PPE_UPD_LDS ? PPE_UPD_CAP : 0u))>;
     // (ATK: the classify body keeps nothing more in LDS than without the monitors, whose counts live in the bins it
     // flushed into its slot before its last barrier; syn_new[4] behind g)
@@ -2782,8 +2801,10 @@ __global__ __launch_bounds__(PPE_FLOW_PS_BLOCK) void ppe_flow_ps_kernel(ppe_flow
         a.t.verdict[p] = st | (act << 8) | (flags << 16);
         atomicAdd(&bins[st | ((flags & 7u) << 5)], 1u);
     }
+#if !defined(PPE_TU_FLOW_PS_ST)  // (with sessions a stream drop changes the action afterwards: every tile once, in finish)
     if (mask != 0ull)  // (wave-uniform; a tile without pending packets was completed by the classify phase)
         compact_tile(a.t.fw_idx, a.t.drop_idx, a.t.tile_cnt, n, 0u, wv, lane, valid, act, ~0u, a.t.part8);
+#endif
     const uint32_t ncr = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(is_new)),
                    ntb = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(tomb));
     if (lane == 0 && ncr) {
@@ -2848,7 +2869,58 @@ __global__ __launch_bounds__(PPE_FLOW_PS_BLOCK) void ppe_flow_ps_kernel(ppe_flow
         if (tid >= 192u && tid < 196u && g[FPG_WORDS + tid - 192u])
             __hip_atomic_fetch_add(&a.k.fatk_slots[3u * (tid - 192u) + 2u], (unsigned long long)g[FPG_WORDS + tid - 192u],
                                    __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#if defined(PPE_TU_FLOW_PS_ST)
+    // the session arrays (keys, four packet words, the stream counters, g, est: 6 BLOCK + PPE_STC_WORDS + 8 words) overlay
+    // the resolve arrays.  The session text zeroes its counters ahead of its first barrier, where other waves may still
+    // be in the loops above: those read bins / lcnt and the resolve g only, neither of which the counters touch
+    static_assert(4u * (6u * BLOCK + PPE_STC_WORDS + 8u) <= 4u * (PPE_NBINS + 32u + 10u * BLOCK + FPG_WORDS + (ATK ? 4u : 0u)),
+                  "the session arrays fit in what the resolve arrays occupy");
+    static_assert(PPE_NBINS + 32u <= 6u * BLOCK && 6u * BLOCK + PPE_STC_WORDS + 8u <= PPE_NBINS + 32u + 10u * BLOCK,
+                  "the stream counters lie behind bins / lcnt and in front of the resolve g");
+    }
+    // between: the session text begins with every wave's drain (vmcnt 0), the workgroup barrier and an agent-scope
+    // acquire-release fence: the verdicts and the LIVE keys finalize stored are read next, and every source's owner is
+    // past ps_store's LDS loads (they stand in front of finalize's own barriers) before a session array is written
+#include "ppe_flow_session_phase.h"
+#endif
 }
+#if defined(PPE_TU_FLOW_PS_ST)
+// ppe_flow_ps_st_kernel (csrc/ppe_kernels_flow_portscan_stream.hip, and with ATK csrc/ppe_kernels_flow_portscan_attack_stream.hip;
+// ppe_flow_stream_portscan, ppe_pick_flow_stream_portscan): [DP_Attack_PacketMonitor,] FlowHandlePacket
+// with PortScan_Detect on its misses, then StreamTcp, as one core running the batch in index order: the reference's
+// default pipeline in one launch of one 1,024-thread workgroup.
+//   classify, setup, resolve, finalize   ppe_flow_ps_kernel's text, with two differences: the list pointers of the classify
+//              arguments and of the tail are NULL, and finalize compacts no tile (a stream drop changes a packet's action
+//              afterwards, so nothing may be in a list before the sessions have spoken; unused list slots and the guard
+//              entries behind them stay untouched);
+//   between    drain, barrier, agent-scope fence (the head of the session text);
+//   session, finish   ppe_flow_st_kernel's text (csrc/ppe_flow_session_phase.h): every packet that ended ACL_FW with
+//              PPE_F_FLOW | PPE_F_TCP steps its flow's session; a packet the detector dropped (status 24), NO_SYN,
+//              ACL_DROP and FLOW_NOMEM have no flow and are not tracked.  A stream drop rewrites the packet's verdict
+//              word only: the flow, the detector's record and the flags stay.  finish compacts every tile, once.
+// The session slot comes from flow_find over the finished table, as in ppe_flow_st_kernel, not from the slot a creator's
+// thread holds: a found packet of the classify phase holds none (FlowFind's slot dies with that phase), so the probe is
+// needed for most packets anyway; one rule for all keeps the text shared, and a creator's probe hits the key its own
+// thread stored (drained and fenced) in its first group.
+// ATK: syncount_accum takes + k from finalize (TCP SYNs that created a flow, per port) and 0 - k from finish (steps
+// SYN_RECV -> ESTABLISHED, on the completing packet's port), both agent-scope atomic adds into slot 0; word 13 of a
+// session record is its creating packet's port.  Without ATK word 13 is always stored as 0 (ppe_ss_pack writes it), as
+// kind 5 stores it.
+// Hang safety: one workgroup; nothing waits on another workgroup and nothing spins.  The loops are the resolve rounds
+// (at most n + 1, an overrun raises PPE_FCTL_ERR and leaves the loop), the sort's log2(np2) (log2(np2) + 1) / 2 stages and
+// the walk (at most n steps: sorted positions below np2); every barrier is reached by all 1,024 threads (the loop
+// conditions around barriers are workgroup-uniform: LDS words read behind a barrier, or n).
+// Per word, what the session phases read and how, beside §5.11's and §5.15's lists:
+//   verdict[]    finalize's plain stores (pending packets) and classify's non-temporal stores (the rest), drained;
+//                plain loads behind the fence; finish stores the stream drops' words, read by nobody here;
+//   keys[]       finalize's LIVE / TOMB stores, drained; flow_find's plain loads behind the fence; nothing stores keys after;
+//   tuple[], hdr[], port bytes   classify's stores drained two fences earlier, or read-only in the launch;
+//   detector records, firstinv   stored by their owners in finalize from LDS; the session phases neither load nor
+//                store them: the LDS they came from is free once finalize's barriers are passed;
+//   sess[]       one walker per slot loads, steps and stores the record (vector loads and stores); a slot finalize made
+//                LIVE in this batch starts from the zero record at its PPE_F_NEWFLOW packet, whatever the words hold;
+//   stc[], cslots[], slot 0's count words, ctl[]   agent-scope atomic adds, read by nobody in the launch.
+#endif
 #endif
 
 #if defined(PPE_TU_FLOW_ST)
@@ -2930,145 +3002,8 @@ __global__ __launch_bounds__(PPE_FLOW_ST_BLOCK) void PPE_FST_KERNEL_NAME(ppe_flo
         }
         flow_finalize_wg<BLOCK, ATK>(f, 1u, bins, lcnt, part, tail[0], *(unsigned long long *)(tail + 2), tail + 4);
     }
-    // ---- session ----
-    // LDS: what the classify phase had in front of the image, free behind the barrier
-    using LI = Lds<BLOCK, true, 4u * PPE_UPD_OWNERS * (1u + (PPE_UPD_LDS ? PPE_UPD_CAP : 0u))>;
-    // (ATK: est[4] behind g, the establishments of this batch per port; the launch's dynamic LDS is the classify
-    // phase's, which these four words do not change)
-    static_assert(8u * BLOCK + 4u * (4u * BLOCK + PPE_STC_WORDS + 4u + (ATK ? 4u : 0u)) <= LI::IMGB,
-                  "the session arrays fit in front of the image");
-    unsigned long long *keys = (unsigned long long *)smem;       // [BLOCK] slot << 32 | index, ~0 for the rest
-    uint32_t *pf = smem + 2u * BLOCK, *sq = pf + BLOCK, *ak = sq + BLOCK, *wp = ak + BLOCK;  // by packet index
-    uint32_t *sc = wp + BLOCK, *g = sc + PPE_STC_WORDS;          // the stream counters; g[0]: drops, g[1]: lost flows
-    const ppe_bdesc &B = a.k.batch[0];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // (the counters lie behind finalize's arrays, which its last loop may still be reading in another wave)
-    static_assert(PPE_NBINS + 32u + BLOCK + 8u <= 6u * BLOCK, "the counters lie behind finalize's arrays");
-    uint32_t *est = g + 4u;  // ATK: SYN_RECV -> ESTABLISHED steps of this batch, by the completing packet's port
-    if (tid < PPE_STC_WORDS + 4u + (ATK ? 4u : 0u)) sc[tid] = 0u;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");
-    const uint32_t n = B.n, ntiles = (n + 63u) >> 6, p = tid;
-    const bool valid = p < n;
-    uint32_t v = valid ? a.t.verdict[p] : 0u;
-    bool tracked = valid && (v & 0xffu) == PPE_ST_ACL_FW &&
-                   ((v >> 16) & (PPE_F_FLOW | PPE_F_TCP)) == (PPE_F_FLOW | PPE_F_TCP);
-    unsigned long long key = ~0ull;
-    if (tracked) {
-        const uint4 t = ((const uint4 *)B.tuple)[p];
-        uint32_t fsip = 0, fports = 0;
-        const int32_t s = flow_find(a.k.flow, flow_hashfn_l4(true, t.x, t.y, t.z & 0xffffu, t.z >> 16), t.x, t.y, t.z, 6u,
-                                    fsip, fports);
-        if (s >= 0) {
-            // the TCP header in the window: behind Ethernet, one VLAN tag if decoded, and the IPv4 header (stride >= 144
-            // holds every byte read here: at most 18 + 60 + 60)
-            const uint8_t *row = B.hdr + (size_t)p * B.stride;
-            const uint32_t l3 = 14u + (((t.w >> 8) & 1u) ? 4u : 0u);
-            const uint8_t *th = row + l3 + 4u * (row[l3] & 15u);
-            const uint32_t wso = PPE_TUPLE_WS(t.w);  // the option's offset from the TCP header, 0: none
-            const uint32_t ws = wso ? (uint32_t)th[wso + 2u] : (uint32_t)PPE_SS_NO_WS;
-            pf[p] = (uint32_t)th[13] | (((v >> 16) & PPE_F_TOCLIENT) ? 0x100u : 0u) | (ws << 16) |
-                    (((v >> 16) & PPE_F_NEWFLOW) ? FST_NEW : 0u);
-            if constexpr (ATK)  // m->input_port: the monitors' port byte of this packet (none: port 0)
-                if (a.k.fatk_pb) pf[p] |= ((uint32_t)a.k.fatk_pb[p] & 3u) << FST_PORT_SHIFT;
-            sq[p] = ((uint32_t)th[4] << 24) | ((uint32_t)th[5] << 16) | ((uint32_t)th[6] << 8) | th[7];
-            ak[p] = ((uint32_t)th[8] << 24) | ((uint32_t)th[9] << 16) | ((uint32_t)th[10] << 8) | th[11];
-            wp[p] = ((uint32_t)th[14] << 8) | th[15] | ((t.w >> 16) << 16);
-            key = ((unsigned long long)(uint32_t)s << 32) | p;
-        } else {  // never: a packet with PPE_F_FLOW has a live flow when finalize is done
-            tracked = false;
-            g[1] = 1u;
-        }
-    }
-    keys[p] = key;
-    // bitonic sort of the keys over the batch's power of two (at least one wave)
-    uint32_t np2 = 64u;
-    while (np2 < n) np2 <<= 1;
-    for (uint32_t k = 2u; k <= np2; k <<= 1) {
-        for (uint32_t j = k >> 1; j > 0u; j >>= 1) {
-            __syncthreads();
-            const uint32_t q = tid ^ j;
-            if (tid < np2 && q > tid) {
-                const unsigned long long x = keys[tid], y = keys[q];
-                if ((x > y) == ((tid & k) == 0u)) {
-                    keys[tid] = y;
-                    keys[q] = x;
-                }
-            }
-        }
-    }
-    __syncthreads();
-    // the walk: the first packet of each slot's group
-    if (tid < np2) {
-        const unsigned long long k0 = keys[tid];
-        const uint32_t slot = (uint32_t)(k0 >> 32);
-        if (k0 != ~0ull && (tid == 0u || (uint32_t)(keys[tid - 1u] >> 32) != slot)) {
-            uint4 *rp = (uint4 *)(a.sess + (size_t)PPE_FLOW_SESS_WORDS * slot);
-            uint32_t w[PPE_FLOW_SESS_WORDS];
-            {
-                const uint4 r0 = rp[0], r1 = rp[1], r2 = rp[2], r3 = rp[3];
-                w[0] = r0.x, w[1] = r0.y, w[2] = r0.z, w[3] = r0.w, w[4] = r1.x, w[5] = r1.y, w[6] = r1.z, w[7] = r1.w;
-                w[8] = r2.x, w[9] = r2.y, w[10] = r2.z, w[11] = r2.w, w[12] = r3.x, w[13] = r3.y, w[14] = r3.z, w[15] = r3.w;
-            }
-            PpeSsn x;
-            ppe_ss_unpack(w, x);
-            uint32_t cport = w[13];  // ATK: flow_item_t.input_port (flow.c:139), the creating packet's port
-#pragma unroll 1
-            for (uint32_t j = tid; j < np2; ++j) {  // (at most n steps: the group ends where the slot changes)
-                const unsigned long long kj = keys[j];
-                if ((uint32_t)(kj >> 32) != slot || kj == ~0ull) break;
-                const uint32_t i = (uint32_t)kj & (BLOCK - 1u);
-                const uint32_t f = pf[i], wl = wp[i];
-                if (f & FST_NEW) x = PpeSsn{};  // FlowAdd gave the flow no session yet: the zero record
-                if constexpr (ATK)
-                    if (f & FST_NEW) cport = (f >> FST_PORT_SHIFT) & 3u;
-                const uint32_t before = x.state;
-                const PpeSsPkt pk = {f & 0xffu, sq[i], ak[i], wl & 0xffffu, wl >> 16, (f >> 16) & 0xffu, (f >> 8) & 1u};
-                sq[i] = ppe_stream_step(x, pk, [&](uint32_t c) { atomicAdd(&sc[c], 1u); });
-                // DP_Attack_SynCountFins (stream-tcp.c:608, :660): the step that completes the handshake, on its packet's port
-                if constexpr (ATK)
-                    if (before == PPE_TCP_SYN_RECV && x.state == PPE_TCP_ESTABLISHED)
-                        atomicAdd(&est[(f >> FST_PORT_SHIFT) & 3u], 1u);
-            }
-            ppe_ss_pack(x, w);
-            if constexpr (ATK) w[13] = cport;
-            rp[0] = make_uint4(w[0], w[1], w[2], w[3]);
-            rp[1] = make_uint4(w[4], w[5], w[6], w[7]);
-            rp[2] = make_uint4(w[8], w[9], w[10], w[11]);
-            rp[3] = make_uint4(w[12], w[13], w[14], w[15]);
-        }
-    }
-    __syncthreads();
-    // ---- finish ----
-    const uint32_t reason = tracked ? sq[p] : 0u;
-    if (reason) {
-        const uint32_t st = reason <= PPE_STC_MIDSTREAM_DISABLE ? reason + 17u : (uint32_t)PPE_ST_STREAM_TRACK_DROP;
-        static_assert(PPE_STC_RST_BUT_NO_SESSION + 17u == PPE_ST_STREAM_RST_NO_SESSION &&
-                      PPE_STC_MIDSTREAM_DISABLE + 17u == PPE_ST_STREAM_MIDSTREAM_OFF, "StateNone's four reasons");
-        const uint32_t fl = (v >> 16) | (st == PPE_ST_STREAM_TRACK_DROP ? reason << PPE_F_STREAM_REASON_SHIFT : 0u);
-        v = st | ((uint32_t)PPE_ACT_DROP << 8) | (fl << 16);
-        a.t.verdict[p] = v;
-    }
-    if (wv < ntiles)  // (wave-uniform)
-        compact_tile(a.fw_idx, a.drop_idx, a.tile_cnt, n, 0u, wv, lane, valid, (v >> 8) & 0xffu, ~0u, a.part8);
-    const uint32_t nd = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(reason != 0u));
-    if (lane == 0 && nd) atomicAdd(&g[0], nd);
-    __syncthreads();
-    if (tid < PPE_STC__COUNT && sc[tid])
-        __hip_atomic_fetch_add(&a.stc[tid], (unsigned long long)sc[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (tid == 64u && g[0]) {  // output_drop_proc instead of the forward the plain phases counted (flow.c:316-319)
-        __hip_atomic_fetch_add(&a.k.cslots[PPE_C_OUT_DROP], (unsigned long long)g[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_fetch_add(&a.k.cslots[PPE_C_OUT_FW], 0ull - (unsigned long long)g[0], __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (tid == 128u && g[1])
-        __hip_atomic_fetch_add(&a.k.flow.ctl[PPE_FCTL_ERR], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if constexpr (ATK)  // syncount_accum -= est[port], modulo 2^64 as the reference's cvmx_atomic_add64 (behind the barrier
-                        // above: every walker's LDS adds are in); slot 0 is the slot this workgroup's classify phase flushed into
-        if (tid >= 192u && tid < 196u && est[tid - 192u])
-            __hip_atomic_fetch_add(&a.k.fatk_slots[3u * (tid - 192u) + 2u], 0ull - (unsigned long long)est[tid - 192u],
-                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // the session and finish phases: text shared with ppe_flow_ps_st_kernel by the preprocessor
+#include "ppe_flow_session_phase.h"
 }
 
 #if PPE_TU_FLOW_ST == 2
@@ -3550,6 +3485,53 @@ extern "C" int ppe_launch_flow_small(
     if (mode == IMG_LDS) hipExtLaunchKernelGGL((ppe_flow_small_kernel<IMG_LDS, PPE_FSM_ATK>), g, b, shmem, s, e0, e1, 0, k);
     else if (mode == IMG_SPLIT) hipExtLaunchKernelGGL((ppe_flow_small_kernel<IMG_SPLIT, PPE_FSM_ATK>), g, b, shmem, s, e0, e1, 0, k);
     else hipExtLaunchKernelGGL((ppe_flow_small_kernel<IMG_GLOBAL, PPE_FSM_ATK>), g, b, shmem, s, e0, e1, 0, k);
+    return (int)hipGetLastError();
+}
+#elif defined(PPE_TU_FLOW_PS_ST)
+// csrc/ppe_kernels_flow_portscan_stream.hip: this file again (as csrc/ppe_kernels_flow_portscan.hip builds it), exporting
+// only the one-launch flow kernel with the port-scan detector inside and the TCP session machine behind it over the
+// three image placements of the flow-table plan, at 1024 threads
+// (csrc/ppe_kernels_flow_portscan_attack_stream.hip, PPE_TU_FLOW_PS == 2: the same kernel with the attack monitors in its
+// classify phase and the syncount_accum counts in its finalize and finish phases, a->fatk_* filled)
+#if PPE_TU_FLOW_PS == 2
+#define PPE_FPS_ATK true
+extern "C" int ppe_launch_flow_stream_portscan_attack(
+#else
+#define PPE_FPS_ATK false
+extern "C" int ppe_launch_flow_stream_portscan(
+#endif
+    const ppe_kargs *a, const ppe_flow_small_tail *t, const ppe_ps_kargs *ps, const ppe_flow_st_args *st, int mode,
+    void *stream, void *ev_start, void *ev_stop) {
+    const hipStream_t s = (hipStream_t)stream;
+    const hipEvent_t e0 = (hipEvent_t)ev_start, e1 = (hipEvent_t)ev_stop;
+    if (a->flow.upd_wgs != 0u || a->nbatch != 1u || a->ring || a->batch[0].n == 0u || a->batch[0].n > PPE_FLOW_PS_MAX ||
+        a->batch[0].n > PPE_FLOW_ST_MAX || a->batch[0].stride < PPE_FLOW_STREAM_MIN_STRIDE || !ps || !st || !st->sess ||
+        !st->stc || !t->verdict)
+        return (int)hipErrorInvalidValue;
+    if (PPE_FPS_ATK && (!a->fatk_st || !a->fatk_slots)) return (int)hipErrorInvalidValue;
+    if (!a->batch[0].tuple && !st->tuple_scratch) return (int)hipErrorInvalidValue;
+    ppe_flow_ps_st_kargs k;
+    k.k = *a;
+    k.t = *t;
+    k.ps = *ps;
+    // the lists are compacted once, by the kernel's last phase: the classify and finalize phases get none
+    k.fw_idx = t->fw_idx;
+    k.drop_idx = t->drop_idx;
+    k.tile_cnt = t->tile_cnt;
+    k.part8 = t->part8;
+    k.t.fw_idx = k.t.drop_idx = k.t.tile_cnt = nullptr;
+    k.t.part8 = nullptr;
+    k.k.batch[0].fw_idx = k.k.batch[0].drop_idx = k.k.batch[0].tile_cnt = nullptr;
+    k.k.batch[0].flags &= ~(uint32_t)PPE_BD_PART8;
+    if (!k.k.batch[0].tuple) k.k.batch[0].tuple = st->tuple_scratch;  // the session phase reads the batch's tuples
+    k.sess = st->sess;
+    k.stc = st->stc;
+    const size_t base = ppe_classify_fixed_lds(PPE_FLOW_PS_BLOCK, PF_HOIST, mode) + ppe_flow_lds_extra();
+    const size_t shmem = mode == IMG_GLOBAL ? base : base + (((size_t)a->stage_words * 4u + 1023u) & ~(size_t)1023u);
+    const dim3 g(1), b(PPE_FLOW_PS_BLOCK);
+    if (mode == IMG_LDS) hipExtLaunchKernelGGL((ppe_flow_ps_st_kernel<IMG_LDS, PPE_FPS_ATK>), g, b, shmem, s, e0, e1, 0, k);
+    else if (mode == IMG_SPLIT) hipExtLaunchKernelGGL((ppe_flow_ps_st_kernel<IMG_SPLIT, PPE_FPS_ATK>), g, b, shmem, s, e0, e1, 0, k);
+    else hipExtLaunchKernelGGL((ppe_flow_ps_st_kernel<IMG_GLOBAL, PPE_FPS_ATK>), g, b, shmem, s, e0, e1, 0, k);
     return (int)hipGetLastError();
 }
 #elif defined(PPE_TU_FLOW_PS)

@@ -385,6 +385,7 @@ EXPORTS = [
     "ppe_format_tcpstream_stat",
     "ppe_flow_stream_attach", "ppe_flow_stream_max", "ppe_flow_stream_dump", "ppe_stream_track_counters_read",
     "ppe_stream_track_counters_clear", "ppe_format_tcpstream_stat_ex", "ppe_flow_stream_monitors",
+    "ppe_flow_stream_portscan",
     "ppe_portscan_create", "ppe_portscan_destroy", "ppe_portscan_attach", "ppe_portscan_clock", "ppe_portscan_set",
     "ppe_portscan_age", "ppe_portscan_info", "ppe_portscan_dump", "ppe_portscan_last_error", "ppe_portscan_prepass_info",
     "ppe_flow_portscan_attach", "ppe_flow_portscan_max", "ppe_flow_portscan_rounds", "ppe_flow_combine",
@@ -395,7 +396,7 @@ EXPORTS = [
     # csrc/ppe_internal.h: the host-only launch planner (internal helpers, not part of the public headers)
     "ppe_plan_image", "ppe_pick_groups", "ppe_pick_portscan", "ppe_pick_portscan_prepass", "ppe_pick_attack", "ppe_pick_attack_flow", "ppe_pick_flow_small",
     "ppe_pick_flow_portscan", "ppe_pick_flow_combined", "ppe_pick_flow_small_attack", "ppe_pick_flow_stream",
-    "ppe_pick_flow_stream_monitors", "ppe_stream_session_step",
+    "ppe_pick_flow_stream_monitors", "ppe_pick_flow_stream_portscan", "ppe_stream_session_step",
     # ppe_acl.h
     "ppe_rule_list_init", "ppe_rule_list_free", "Rule_add", "Rule_del_by_id", "Rule_del_all",
     "Rule_duplicate_check", "Rule_Load_Line", "ppe_rule_load_file", "DP_Acl_Rule_Init", "DP_Acl_Load_Rule",
@@ -497,6 +498,8 @@ def _open(p: Path, mode, strict: bool = True) -> C.CDLL:
         "ppe_pick_flow_stream": ([u32, C.c_int, u32, u32, u32, u32, C.c_int, C.c_int], u32),
         "ppe_pick_flow_stream_monitors": ([u32, C.c_int, u32, u32, u32, u32, C.c_int, C.c_int, u32], u32),
         "ppe_flow_stream_monitors": ([vp, u32], C.c_int),
+        "ppe_pick_flow_stream_portscan": ([u32, C.c_int, u32, u32, u32, u32, C.c_int, C.c_int, u32, u32, u32, u32], u32),
+        "ppe_flow_stream_portscan": ([vp, u32], C.c_int),
         "ppe_flow_portscan_rounds": ([vp, C.POINTER(u32)], C.c_int),
         "ppe_flow_combine": ([vp, u32], C.c_int),
         "ppe_pick_flow_combined": ([u32, C.c_int, u32], u32),

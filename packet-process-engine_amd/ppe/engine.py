@@ -230,8 +230,10 @@ class Engine:
         one-launch kernel with the port-scan detector inside, (3, 1) that kernel with the flow-attached monitors in it as
         well (flow_combine), (4, 1) the one-launch kernel with the flow-attached monitors in it (chunks of
         classify_flow_host_ports only), (5, 1) the one-launch kernel with the TCP session machine behind it
-        (flow_stream), (6, 1) that kernel with the flow-attached monitors in it as well (flow_stream_monitors), (0, 2)
-        the two launches, (0, 0) before the first."""
+        (flow_stream), (6, 1) that kernel with the flow-attached monitors in it as well (flow_stream_monitors), (7, 1)
+        the one-launch kernel with the port-scan detector inside and the session machine behind it
+        (flow_stream_portscan), (8, 1) that kernel with the flow-attached monitors in it as well, (0, 2) the two
+        launches, (0, 0) before the first."""
         k, n = C.c_uint32(9), C.c_uint32(9)
         self._check(self.lib.ppe_flow_launch_info(self.ctx, C.byref(k), C.byref(n)), "ppe_flow_launch_info")
         return k.value, n.value
@@ -330,6 +332,13 @@ class Engine:
         decrements (a completed handshake, a flow aged out in its handshake); 0 (a new context): such a batch is
         refused."""
         self._check(self.lib.ppe_flow_stream_monitors(self.ctx, int(on)), "ppe_flow_stream_monitors")
+
+    def flow_stream_portscan(self, on: int) -> None:
+        """ppe_flow_stream_portscan: 1, a flow batch with sessions attached and a port-scan table flow-attached (able 1)
+        runs the table, the detector on its misses and the sessions in one launch (flow_launch_info (7, 1)); with attack
+        monitors flow-attached as well, and flow_combine and flow_stream_monitors both on, the reference's whole default
+        pipeline in one launch ((8, 1)); 0 (a new context): such a batch is refused."""
+        self._check(self.lib.ppe_flow_stream_portscan(self.ctx, int(on)), "ppe_flow_stream_portscan")
 
     def flow_stream_max(self) -> int:
         """ppe_flow_stream_max: the packets one device flow batch takes with sessions attached."""
